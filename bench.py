@@ -15,9 +15,19 @@ step     : one surface-reconstruction epoch over the whole field
 N GPUs   : heliostats are sharded over ranks exactly like RestrictedDistributedSampler
            (heliostat i -> rank i mod N); total work is fixed  => "scaling": "strong".
 
-Every rank draws ITS rows of the field-wide seed-7 sample, so an N-rank run traces exactly the rays of the 1-rank run; the line
-carries a checksum of the reduced flux ("sharding_check") and, at N > 1, rank 0 re-traces the whole field alone and the run fails
-when the reduced flux differs from it by more than 2e-6.
+Every rank draws ITS rows of the field-wide seed-7 sample, so an N-rank run traces exactly the rays of the 1-rank run.
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, ms_per_step, dtype, config).
+--full adds everything else, after the headline region: a second timed region with HIP events per step and per trace call, a
+forward-only region, back-to-back kernel times, the roofline, the oracle stamp of the timed rays ("check"), a checksum of the
+reduced flux ("sharding_check": at N > 1 rank 0 re-traces the whole field alone and the run fails when the reduced flux differs
+from it by more than 2e-6) and the CPU baselines.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files (all inputs are seeded, so two builds can be
+compared file by file): per_target_flux [T,256,256] (what the step returns), loss_per_heliostat [H], control_points_grad and
+control_points [H,4,nu,nv,3] (the gradient of the step's loss and the parameters after its Adam update) and flux_sample
+[32,256,256] (the traced bitmaps of 32 heliostats).  The heliostats of a sample are the first ones of a seed-0 permutation of
+the field, sorted; per-heliostat arrays are sampled that way only when the whole field would exceed their share of 64 MB.
 
 Prints ONE JSON line on rank 0.
 """
@@ -50,10 +60,55 @@ def parse():
     ap.add_argument("--rays", type=int, default=100, help="rays per surface point (Sun.number_of_rays)")
     ap.add_argument("--n-eval", type=int, default=50, help="evaluation points per facet per direction")
     ap.add_argument("--n-cp", type=int, default=10, help="NURBS control points per facet per direction")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle comparison of the timed rays")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: event-timed and forward-only regions, kernel times, roofline, checks, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-check", action="store_true", help="(--full) skip the oracle comparison of the timed rays")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) target CPU time of the baseline sample")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+FLUX_SAMPLE = 32            # heliostats whose traced bitmaps are written
+
+
+def sample_rows(n_total, k):
+    """The first ``k`` of a seed-0 permutation of ``range(n_total)``, sorted (all rows when ``k >= n_total``)."""
+    if k >= n_total:
+        return torch.arange(n_total)
+    return torch.randperm(n_total, generator=torch.Generator().manual_seed(0))[:k].sort().values
+
+
+def step_outputs(last, cp, n_total):
+    """The arrays a caller of the timed step receives, from its last call, as float32 numpy arrays on every rank (the per-heliostat
+    rows are gathered from their owners: a collective, every rank takes part).  Row-sampled to stay inside ``DUMP_BYTES``."""
+    from artist_amd.distributed import gather_owned_rows
+
+    def rows(local, share):
+        full = gather_owned_rows(local.detach().float().contiguous(), n_total)
+        row_bytes = 4 * max(1, full[0].numel())
+        idx = sample_rows(n_total, max(1, share // row_bytes)).to(full.device)
+        return full.index_select(0, idx).cpu().numpy()
+
+    flux_rows = sample_rows(n_total, FLUX_SAMPLE).to(last["flux"].device)
+    flux = gather_owned_rows(last["flux"].detach(), n_total)
+    return {"per_target_flux": last["per_target"].detach().float().cpu().numpy(),
+            "loss_per_heliostat": rows(last["loss"], 4 << 20),
+            "control_points_grad": rows(cp.grad, 24 << 20),
+            "control_points": rows(cp, 24 << 20),
+            "flux_sample": flux.index_select(0, flux_rows).float().cpu().numpy()}
+
+
+def write_outputs(outputs, directory):
+    import numpy as np
+
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_BYTES, f"outputs of {total} bytes exceed the {DUMP_BYTES}-byte budget"
+    out = pathlib.Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def cpu_baseline(args, cp_host, canting, transl, uv, orientation, incident, planar, seconds):
@@ -249,6 +304,7 @@ def main():
     from artist_amd import ops
     from artist_amd.flux import FluxCrop, FluxCropPixelLoss
     target = None
+    last = {} if args.dump_outputs else None          # --dump-outputs: the latest training step's outputs (references, no copies)
 
     def forward():
         # evaluation + alignment in one kernel (the kinematics is fixed during a surface reconstruction)
@@ -268,8 +324,10 @@ def main():
             if backward:
                 # the epoch's epilogue (surface_reconstructor.py:575-590, 664-676): crop around the centre of mass,
                 # pixel loss against the (cropped) measured flux
-                loss = FluxCropPixelLoss.apply(flux, crop_dims, target, 6.0, 6.0).sum()      # one fused pass per direction
-                loss.backward()
+                losses = FluxCropPixelLoss.apply(flux, crop_dims, target, 6.0, 6.0)      # one fused pass per direction
+                losses.sum().backward()
+                if last is not None:
+                    last.update(flux=flux, loss=losses, per_target=per_target)
                 # surface_reconstructor.py:767-777: every rank ends with the field's gradient.  The shards are
                 # row-disjoint, so the reference's all_reduce(SUM) is an all-gather of the own rows (half the bytes)
                 pending_grad = gather_owned_rows(cp.grad, H_total, async_op=True)    # travels during the optimiser step
@@ -313,6 +371,38 @@ def main():
         step(True)
     # ---- region 1, the headline: EXACTLY K steps between barrier + synchronize on both sides, nothing else inside ----
     dt = timed(lambda: step(True), args.steps)
+    # ---- what the last timed step computed, taken before anything else runs ----
+    if last is not None:
+        outputs = step_outputs(last, cp, H_total)
+        last = None                                   # later steps (--full) record nothing
+        if rank == 0:
+            write_outputs(outputs, args.dump_outputs)
+        del outputs
+    total_rays = H_total * R * P
+    headline = {
+        "metric": "traced rays/s fwd+bwd, 1000-heliostat NURBS field",
+        "value": total_rays * args.steps / dt,
+        "unit": "rays/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"metric config: {H_total} heliostats x {R} rays/point x {P} points "
+                               f"({total_rays:.3g} rays/step), {args.n_cp}x{args.n_cp} degree-3 NURBS, 256x256 bitmap, "
+                               "surface-reconstruction epoch fwd+bwd",
+                   "heliostats": H_total, "rays_per_point": R, "points_per_heliostat": P,
+                   "parallelism": f"heliostat-sharded dp{world}", "heliostats_per_rank": H},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1 or rehearse:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- region 2, the same K steps once more with HIP events: one pair per STEP (the median step) and one pair around each
     # of the two trace calls, on the stream they are launched on (ops.record_launch_events: two event records per call, no
     # synchronisation) - the roofline's launch durations.  Outside the headline region (round 3 recorded them inside it).
@@ -429,27 +519,12 @@ def main():
                              "tolerance": 2e-6, "ok": bool(rel < 2e-6)})
 
     if rank == 0:
-        total_rays = H_total * R * P
         out = {
-            "metric": "traced rays/s fwd+bwd, 1000-heliostat NURBS field",
-            "value": total_rays * args.steps / dt,
-            "unit": "rays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
+            **headline,
             # region 2 (same K steps again, one HIP-event pair per step on the launch stream): median and spread of a step
             "step_events": {"median_ms": median_step_ms, "min_ms": step_ms[0], "max_ms": step_ms[-1],
                             "wall_ms_per_step": dt_events / args.steps * 1e3,
                             "what": "second timed region of K steps, HIP events per step + per trace call; the headline region holds no event record"},
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"metric config: {H_total} heliostats x {R} rays/point x {P} points "
-                                   f"({total_rays:.3g} rays/step), {args.n_cp}x{args.n_cp} degree-3 NURBS, 256x256 bitmap, "
-                                   "surface-reconstruction epoch fwd+bwd",
-                       "heliostats": H_total, "rays_per_point": R, "points_per_heliostat": P,
-                       "parallelism": f"heliostat-sharded dp{world}", "heliostats_per_rank": H},
             "fwd_only": {"value": total_rays * args.steps / dt_fwd, "unit": "rays/s",
                          "ms_per_step": dt_fwd / args.steps * 1e3},
             "kernels": {"where": "HIP events around art_trace_fwd / art_trace_bwd on their launch stream, mean over the K steps of the "

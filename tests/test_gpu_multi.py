@@ -27,7 +27,7 @@ def test_bench_shards_over_the_visible_gpus():
     N = min(count, int(os.environ.get("ARTIST_TEST_MAX_RANKS", "4")))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     env.pop("ARTIST_BENCH_BACKEND", None)                                  # RCCL, not the gloo rehearsal
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(N), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(N), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     tail = "\n".join((res.stdout + "\n" + res.stderr).splitlines()[-40:])
     assert res.returncode == 0, f"bench.py --gpus {N} failed (rc {res.returncode}):\n{tail}"

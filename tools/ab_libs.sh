@@ -1,5 +1,5 @@
 # same-box A/B of library builds: usage  bash tools/ab_libs.sh name...   (artist_amd/libablate_<name>.so; "main" = the product library)
-run() { for h in 1000 125; do timeout -k 10 200 python bench.py --heliostats $h --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  H', d['config']['heliostats'], 'fwd', round(d['kernels']['trace_fwd_ms'],4), 'bwd', round(d['kernels']['trace_bwd_ms'],4), 'step', round(d['ms_per_step'],4))" || return 1; done
+run() { for h in 1000 125; do timeout -k 10 200 python bench.py --heliostats $h --steps 10 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  H', d['config']['heliostats'], 'fwd', round(d['kernels']['trace_fwd_ms'],4), 'bwd', round(d['kernels']['trace_bwd_ms'],4), 'step', round(d['ms_per_step'],4))" || return 1; done
   timeout -k 10 300 python tools/config_bench.py 2>/dev/null | grep "^{" | python -c "
 import sys,json
 for l in sys.stdin:

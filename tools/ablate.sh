@@ -17,6 +17,6 @@ if [ "$1" = build ]; then
 fi
 for v in $VARIANTS; do
   name=${v%%:*}
-  out=$(ARTIST_HIP_LIB=$PWD/tools/bin/libabl_$name.so timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-check "${@:2}" 2>/dev/null | tail -1)
+  out=$(ARTIST_HIP_LIB=$PWD/tools/bin/libabl_$name.so timeout -k 10 200 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-check "${@:2}" 2>/dev/null | tail -1)
   echo "$name $(echo "$out" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); k=d["kernels"]; print("fwd %.3f ms  bwd %.3f ms" % (k["trace_fwd_ms"], k["trace_bwd_ms"]))')"
 done

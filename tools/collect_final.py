@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""gpurun_out/final_* (tools/final_pass.sh on the GPU box) -> profiles/<round>_* : the summaries the round's DESIGN.md cites.
+"""$OUT/final_* (tools/final_pass.sh; OUT defaults to tools_out/) -> profiles/<round>_* : the summaries the round's DESIGN.md cites.
 usage: python tools/collect_final.py r04"""
-import pathlib, shutil, sys
+import os, pathlib, shutil, sys
 rnd = sys.argv[1]
 root = pathlib.Path(__file__).resolve().parent.parent
-src, dst = root / "gpurun_out", root / "profiles"
+src, dst = pathlib.Path(os.environ.get("OUT", root / "tools_out")), root / "profiles"
 names = {"final_bench.json": "bench_line.json", "final_bench_h125.json": "bench_h125.json", "final_bench_config4.json": "bench_config4.json",
          "final_config_bench.jsonl": "config_bench.jsonl", "final_bench_2rank_gloo.log": "bench_2rank_gloo.log",
          "final_bench_rccl_world1.log": "bench_rccl_world1.log", "final_blocking_bench.json": "blocking_bench.json",

@@ -2,11 +2,12 @@
 # Per-kernel average durations of a short bench run (rocprofv3 --kernel-trace --stats), top 16.  GPU box only.
 # usage: bash tools/kstats.sh <tag> [bench args]
 R=$GRAFT_REPO_ROOT; tag=$1; shift
+OUT=${OUT:-$R/tools_out}; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/ks_$tag -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-check "$@" > $R/gpurun_out/ks_$tag.log 2>&1 || echo "rocprof failed"
-f=$(find $R/gpurun_out/ks_$tag -name "*kernel_stats.csv" | head -1)
-t=$(find $R/gpurun_out/ks_$tag -name "*kernel_trace.csv" | head -1)
-python3 - "$f" "$t" "$R/gpurun_out/ks_$tag.log" <<'PY'
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks_$tag -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-check "$@" > $OUT/ks_$tag.log 2>&1 || echo "rocprof failed"
+f=$(find $OUT/ks_$tag -name "*kernel_stats.csv" | head -1)
+t=$(find $OUT/ks_$tag -name "*kernel_trace.csv" | head -1)
+python3 - "$f" "$t" "$OUT/ks_$tag.log" <<'PY'
 import csv,json,sys
 rows=list(csv.DictReader(open(sys.argv[1])))
 for r in rows[:16]:

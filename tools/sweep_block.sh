@@ -5,7 +5,7 @@ export ARTIST_HIP_DEBUG=1   # the library reads its ARTIST_HIP_* knobs only in d
 cd "$(dirname "$0")/.."
 run() {  # label, env assignments...
   label=$1; shift
-  out=$(env "$@" timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1)
+  out=$(env "$@" timeout -k 10 200 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline 2>/dev/null | tail -1)
   echo "$label $(echo "$out" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); k=d["kernels"]; print("fwd %.3f ms  bwd %.3f ms  step %.3f ms" % (k["trace_fwd_ms"], k["trace_bwd_ms"], d["ms_per_step"]))')"
 }
 run "block=1024 (default)        " ARTIST_X=0
