@@ -75,6 +75,13 @@ SIGNATURES = {
     "art_strerror": [_c_int],
 }
 
+# The distortion sampler, declared in include/artist_hip_sampler.h (a header of its own, so that the list above stays the one of
+# artist_hip.h); bound by lib() like SIGNATURES, restype int.
+_c_flt = ctypes.c_float
+SAMPLER_SIGNATURES = {
+    "art_sample_distortions": [_c_i64, _ptr, _c_i64, _c_i64, _c_i64, _c_flt, _c_flt, _c_flt, _c_flt, _c_flt, _ptr, _ptr],
+}
+
 _LIB = None
 
 
@@ -106,7 +113,7 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(str(LIB_PATH))
     except OSError as exc:  # pragma: no cover - depends on the host
         raise ArtistHipError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in (*SIGNATURES.items(), *SAMPLER_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as exc:

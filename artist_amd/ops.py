@@ -17,7 +17,8 @@ import torch
 from . import _lib
 
 __all__ = ["trace_rays", "nurbs_surface_points_and_normals", "per_target_sum", "align_surfaces", "TraceRays",
-           "NurbsEval", "AlignSurfaces", "check_async_errors", "record_launch_events"]
+           "NurbsEval", "AlignSurfaces", "check_async_errors", "record_launch_events",
+           "sample_distortions"]
 
 
 def _stream(device: torch.device) -> int:
@@ -176,6 +177,41 @@ def reflect_directions(incident: torch.Tensor, normals: torch.Tensor) -> torch.T
     with torch.cuda.device(dev):
         rc = _lib.lib().art_reflect(incident.data_ptr(), normals.data_ptr(), H, P, out.data_ptr(), _stream(dev))
     _lib.check(rc, "art_reflect")
+    return out
+
+
+def sample_distortions(rows, number_of_rays: int, number_of_points: int, seed: int, loc, scale_tril, device) -> torch.Tensor:
+    """Rows ``rows`` of the Gaussian sun-shape sample, ``[len(rows), R, P, 2]`` fp32 with ``(u, e)`` interleaved, drawn in one
+    launch on the current stream of ``device`` (``art_sample_distortions``, include/artist_hip_sampler.h).  Row ``rows[k]``
+    comes from a Philox stream keyed by ``(seed, rows[k])``: the same bits whatever the other rows of the call.
+
+    ``loc`` (2 values) and ``scale_tril`` (2x2, lower triangular) are HOST values: the call reads nothing back from the device.
+    ``rows`` is a list of ints or an integer tensor (a list travels through pinned memory, without a synchronisation)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.ArtistHipError(
+            f"artist_amd ops run on the GPU only (sampler asked for {dev}); there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    R, P = int(number_of_rays), int(number_of_points)
+    if R < 0 or P < 0:
+        raise ValueError(f"number_of_rays and number_of_points must be >= 0, got {R}, {P}")
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype.is_floating_point or rows.dim() != 1:
+            raise ValueError("rows must be a 1-D integer tensor or a list of ints")
+        rows_t = rows.to(dev, torch.int64).contiguous() if rows.device == dev else \
+            rows.to(torch.int64).contiguous().pin_memory().to(dev, non_blocking=True)
+    else:
+        rows_t = torch.tensor([int(r) for r in rows], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    (lu, le), ((l00, _), (l10, l11)) = [float(v) for v in loc], [[float(v) for v in r] for r in scale_tril]
+    n = int(rows_t.shape[0])
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed as a 64-bit two's-complement value
+    seed = seed - (1 << 64) if seed >= (1 << 63) else seed
+    out = torch.empty((n, R, P, 2), dtype=torch.float32, device=dev)
+    with _launch("art_sample_distortions", dev):
+        rc = _lib.lib().art_sample_distortions(int(seed), rows_t.data_ptr(), n, R, P, lu, le, l00, l10, l11, out.data_ptr(),
+                                               _stream(dev))
+    _lib.check(rc, "art_sample_distortions")
     return out
 
 

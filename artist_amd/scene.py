@@ -18,12 +18,22 @@ import torch
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nurbs_control_points
 
 
+#: Distortion samplers of :class:`Sun` on the device: ``"torch"`` (the default: one seeded ``torch.randn`` per heliostat row)
+#: and ``"hip"`` (``art_sample_distortions``: one launch, a Philox stream per (seed, row), with a per-sun sample cache).
+SAMPLERS = ("torch", "hip")
+
+
 class Sun:
     """Gaussian sun shape; ``get_distortions`` = seeded ``MultivariateNormal`` sample permuted to
-    ``(u, e)`` views of one interleaved buffer (artist/scene/sun.py:96-119, 199-234)."""
+    ``(u, e)`` views of one interleaved buffer (artist/scene/sun.py:96-119, 199-234).
+
+    ``sampler`` chooses how a GPU-resident sun draws (``SAMPLERS``); it may be set on a light source that is already
+    loaded.  With ``"hip"`` the last sample is kept (one per sun) and handed out again, without a launch or a
+    synchronisation, to every draw with the same (seed, rows, number of rays and points, device, law): the views it
+    returns are SHARED between those callers and must not be written (a write is noticed and makes the next draw anew)."""
 
     def __init__(self, number_of_rays: int, distribution_parameters: dict | None = None,
-                 device: torch.device | None = None) -> None:
+                 device: torch.device | None = None, sampler: str = "torch") -> None:
         params = dict(distribution_type="normal", mean=0.0, covariance=4.3681e-06)
         params.update(distribution_parameters or {})
         if params["distribution_type"] != "normal":
@@ -33,15 +43,39 @@ class Sun:
         mean = torch.tensor([params["mean"], params["mean"]], dtype=torch.float, device=device)
         cov = torch.tensor([[params["covariance"], 0], [0, params["covariance"]]], dtype=torch.float, device=device)
         self.distribution = torch.distributions.MultivariateNormal(mean, cov)
+        self._law = None            # (distribution, tensor versions, host law) - see _host_law
+        self._cache = None          # (key, buffer, buffer version) of the last "hip" draw
+        self._sampler = None
+        self.sampler = sampler
+
+    @property
+    def sampler(self) -> str:
+        return self._sampler
+
+    @sampler.setter
+    def sampler(self, name: str) -> None:
+        if name not in SAMPLERS:
+            raise ValueError(f"Unknown distortion sampler {name!r}; expected one of {SAMPLERS}.")
+        if name != self._sampler:
+            self._sampler = name
+            self._cache = None
+
+    def clear_distortion_cache(self) -> None:
+        """Drop the kept ``"hip"`` sample (its memory is freed once no caller holds a view of it)."""
+        self._cache = None
 
     @classmethod
-    def from_hdf5(cls, config_file, light_source_name: str | None = None, device: torch.device | None = None) -> "Sun":
+    def from_hdf5(cls, config_file, light_source_name: str | None = None, device: torch.device | None = None,
+                  sampler: str = "torch") -> "Sun":
         """artist/scene/sun.py:121-197 (``config_file`` = the light source's own group)."""
         from . import scenario
         t = scenario.read_light_source(config_file, light_source_name)
-        return cls(number_of_rays=t["number_of_rays"], distribution_parameters=t["distribution_parameters"], device=device)
+        return cls(number_of_rays=t["number_of_rays"], distribution_parameters=t["distribution_parameters"], device=device,
+                   sampler=sampler)
 
     def get_distortions(self, number_of_points: int, number_of_active_heliostats: int, random_seed: int = 7):
+        if self._sampler == "hip":
+            return self._hip_rows(range(number_of_active_heliostats), number_of_points, random_seed)
         loc = self.distribution.loc
         if loc.device.type == "cpu":
             torch.manual_seed(random_seed)
@@ -55,11 +89,16 @@ class Sun:
         """Rows ``rows`` of the ``[H,R,P]`` distortion views when the light source lives on the GPU (None on the CPU: the
         caller then slices the reference's one seeded stream, ``artist_amd.sampling.DistortionsDataset``).
 
-        On the device every heliostat sample has a Philox stream of its own, keyed by (seed, row): a rank that owns
+        On the device every heliostat sample has a stream of its own, keyed by (seed, row): a rank that owns
         some of the heliostats draws exactly its rows, bit-identical to the rows of an unsharded draw,
         and nothing of size ``[H,R,P]`` exists anywhere.  Same law as ``MultivariateNormal.sample``
         (``loc + scale_tril @ eps``), written element-wise: the batched 2x2 matrix-vector product of torch's
-        ``MultivariateNormal.sample`` faulted on ROCm for ~1e7 and more samples."""
+        ``MultivariateNormal.sample`` faulted on ROCm for ~1e7 and more samples.
+
+        ``sampler == "torch"``: a seeded ``torch.randn`` per row; ``"hip"``: ``art_sample_distortions`` (Philox4x32-10
+        keyed by (seed, row)), cached per sun (class docstring), and no CPU fallback."""
+        if self._sampler == "hip":
+            return self._hip_rows(rows, number_of_points, random_seed)
         loc, tril = self.distribution.loc, self.distribution.scale_tril
         if loc.device.type == "cpu":
             return None
@@ -79,16 +118,53 @@ class Sun:
         distortions_u, distortions_e = out.permute(3, 0, 1, 2)
         return distortions_u, distortions_e
 
+    def _host_law(self):
+        """``(loc, scale_tril)`` of the current distribution as host floats.  Read from the device (one synchronisation)
+        only when ``distribution`` is a new object or one of its two tensors was written since the last read."""
+        dist = self.distribution
+        loc, tril = dist.loc, dist.scale_tril
+        versions = (loc._version, tril._version)
+        kept = self._law
+        if kept is not None and kept[0] is dist and kept[1] == versions:
+            return kept[2]
+        if tuple(loc.shape) != (2,) or tuple(tril.shape) != (2, 2):
+            raise ValueError(f"the sun's distribution must be a single 2-D normal, got loc {tuple(loc.shape)}, "
+                             f"scale_tril {tuple(tril.shape)}")
+        v = torch.cat((loc.detach().reshape(-1), tril.detach().reshape(-1))).float().cpu().tolist()
+        law = ((v[0], v[1]), ((v[2], v[3]), (v[4], v[5])))
+        self._law = (dist, versions, law)
+        return law
+
+    def _hip_rows(self, rows, number_of_points: int, random_seed: int):
+        from . import _lib, ops
+        loc = self.distribution.loc
+        if loc.device.type != "cuda":
+            raise _lib.ArtistHipError(f"Sun(sampler='hip') draws on the GPU only (the light source is on {loc.device}); "
+                                      "there is no CPU fallback")
+        rows = tuple(int(r) for r in rows)
+        law = self._host_law()
+        key = (int(random_seed), rows, int(self.number_of_rays), int(number_of_points), loc.device, law)
+        kept = self._cache
+        if kept is not None and kept[0] == key and kept[1]._version == kept[2]:
+            buf = kept[1]
+        else:
+            self._cache = None          # the old sample goes first: at most one per sun is alive while the new one is drawn
+            buf = ops.sample_distortions(rows, key[2], key[3], key[0], law[0], law[1], loc.device)
+            self._cache = (key, buf, buf._version)
+        distortions_u, distortions_e = buf.permute(3, 0, 1, 2)
+        return distortions_u, distortions_e
+
 
 class LightSourceArray:
     def __init__(self, light_source_list) -> None:
         self.light_source_list = light_source_list
 
     @classmethod
-    def from_hdf5(cls, config_file, device: torch.device | None = None) -> "LightSourceArray":
-        """artist/scene/light_source_array.py:48-98."""
+    def from_hdf5(cls, config_file, device: torch.device | None = None, sampler: str = "torch") -> "LightSourceArray":
+        """artist/scene/light_source_array.py:48-98 (``sampler``: see :class:`Sun`)."""
         from . import scenario
-        return cls([Sun(number_of_rays=s["number_of_rays"], distribution_parameters=s["distribution_parameters"], device=device)
+        return cls([Sun(number_of_rays=s["number_of_rays"], distribution_parameters=s["distribution_parameters"], device=device,
+                        sampler=sampler)
                     for s in scenario.read_light_sources(config_file)])
 
 
