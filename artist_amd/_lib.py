@@ -82,6 +82,13 @@ SAMPLER_SIGNATURES = {
     "art_sample_distortions": [_c_i64, _ptr, _c_i64, _c_i64, _c_i64, _c_flt, _c_flt, _c_flt, _c_flt, _c_flt, _ptr, _ptr],
 }
 
+# The surface regularisers, declared in include/artist_hip_regularizers.h (a header of its own for the same reason); bound by
+# lib() like SIGNATURES, restype int.
+REGULARIZER_SIGNATURES = {
+    "art_surface_regularizers_fwd": [_ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr],
+    "art_surface_regularizers_bwd": [_ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr],
+}
+
 _LIB = None
 
 
@@ -113,7 +120,7 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(str(LIB_PATH))
     except OSError as exc:  # pragma: no cover - depends on the host
         raise ArtistHipError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, argtypes in (*SIGNATURES.items(), *SAMPLER_SIGNATURES.items()):
+    for name, argtypes in (*SIGNATURES.items(), *SAMPLER_SIGNATURES.items(), *REGULARIZER_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as exc:

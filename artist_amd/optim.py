@@ -5,14 +5,18 @@
 weight decay and ``maximize`` are honoured as well), is a ``torch.optim.Optimizer`` - ``param_groups``, ``state_dict``, learning-rate
 schedulers and ``zero_grad`` work as with torch's - and keeps torch's state layout (``step``, ``exp_avg``, ``exp_avg_sq``).
 The update rule is ``torch.optim.adam._single_tensor_adam`` in fp32; tests compare it with torch's over several steps.
+
+``SmoothnessRegularizer`` and ``IdealSurfaceRegularizer`` (``artist_amd.regularizers``) are exported here as well, where the
+reference has them (``artist.optim``).
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
+from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer
 
-__all__ = ["Adam"]
+__all__ = ["Adam", "SmoothnessRegularizer", "IdealSurfaceRegularizer"]
 
 
 class Adam(torch.optim.Optimizer):
