@@ -13,6 +13,7 @@ backward, behind ARTIST's own call surface:
     artist_amd.optim.Adam           <-> torch.optim.Adam as the reconstructors use it (the epoch's optimiser step)
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer
                                     <-> artist.optim.SmoothnessRegularizer, IdealSurfaceRegularizer (the epoch's regularisers)
+    artist_amd.SurfaceGenerator     <-> artist.scenario.surface_generator.SurfaceGenerator (+ fit_nurbs_batch: all facets at once)
 
 All arithmetic runs in hand-written HIP kernels (``artist_amd/csrc``) reached through the C ABI in
 ``include/artist_hip.h``; there is no CPU fallback.
@@ -28,5 +29,6 @@ from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer, surfac
 from .raytracing import HeliostatRayTracer  # noqa: F401
 from .scenario import Scenario, open_scenario_file  # noqa: F401
 from .sampling import DistortionsDataset, RestrictedDistributedSampler  # noqa: F401
+from .surface_generator import FittedFacet, SurfaceGenerator  # noqa: F401
 
 __version__ = "0.1.0"

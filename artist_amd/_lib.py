@@ -89,6 +89,18 @@ REGULARIZER_SIGNATURES = {
     "art_surface_regularizers_bwd": [_ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr],
 }
 
+# Batched NURBS surface fitting, declared in include/artist_hip_surface_fit.h (a header of its own for the same reason); bound by
+# lib() like SIGNATURES, restype int (art_surface_fit_table_words: int64).
+SURFACE_FIT_SIGNATURES = {
+    "art_surface_fit_table_words": [_c_int, _c_int],
+    "art_surface_fit_prepare": [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "art_surface_fit_loss_grad": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int,
+                                  _ptr, _ptr, _ptr, _ptr, _ptr],
+    "art_surface_fit_run": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _c_i64,
+                            _c_int, _c_int, _c_int, _c_i64, _c_dbl, _c_i64, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_int, _c_int, _c_int,
+                            _c_dbl, _c_i64, _c_dbl, _c_int, _c_i64, _c_dbl, _c_dbl, _ptr],
+}
+
 _LIB = None
 
 
@@ -120,14 +132,16 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(str(LIB_PATH))
     except OSError as exc:  # pragma: no cover - depends on the host
         raise ArtistHipError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, argtypes in (*SIGNATURES.items(), *SAMPLER_SIGNATURES.items(), *REGULARIZER_SIGNATURES.items()):
+    for name, argtypes in (*SIGNATURES.items(), *SAMPLER_SIGNATURES.items(), *REGULARIZER_SIGNATURES.items(),
+                           *SURFACE_FIT_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as exc:
             raise ArtistHipError(f"{LIB_PATH} does not export {name}") from exc
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "art_strerror"
-                      else ctypes.c_int64 if name in ("art_blocking_workspace_bytes", "art_trace_bwd_scratch_floats", "art_trace_bwd_scratch_need")
+                      else ctypes.c_int64 if name in ("art_blocking_workspace_bytes", "art_trace_bwd_scratch_floats", "art_trace_bwd_scratch_need",
+                                                     "art_surface_fit_table_words")
                       else ctypes.c_int)
     if handle.art_abi_version() != ABI_VERSION:
         raise ArtistHipError(f"ABI mismatch: library {handle.art_abi_version()} vs binding {ABI_VERSION}")

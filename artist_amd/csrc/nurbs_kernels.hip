@@ -14,8 +14,8 @@
 //    itself (row length = index of the first point whose u differs from point 0's; then every point is compared with
 //    (u of its row's first point, v of its column's first point)): no flag in the API, no host synchronisation, and points
 //    that are not a grid simply take the other scheme.
-//  * SCATTERED.  Arbitrary evaluation points (SurfaceGenerator.fit_nurbs evaluates at deflectometry points,
-//    artist/field/surface_generator.py:133-202): one thread owns one evaluation point, gathers its (p+1)(q+1) control points
+//  * SCATTERED.  Arbitrary evaluation points (callers that evaluate at measured positions; SurfaceGenerator's fit itself runs in
+//    surface_fit_kernels.hip, whose generic-optimiser tests compare against this scheme): one thread owns one evaluation point, gathers its (p+1)(q+1) control points
 //    from LDS; backward privatises the facet's gradient net in LDS in DOUBLE (ds_add_f64 retires a wave instruction in ~25
 //    cycles, ds_add_f32 needs ~193: tools/lds_atomic_bench.hip) - the order of those adds is not fixed, the result is the same
 //    to fp32 output precision but not bit-reproducible.
@@ -38,11 +38,10 @@
 #include <algorithm>
 
 #include "launch_common.hpp"
-#include "ray_math.hpp"      // div_noscale: n / a bit for bit, without the range scaling of the IEEE sequence
+#include "nurbs_basis.hpp"   // find_span, basis<> (A2.3), norm3 - shared with surface_fit_kernels.hip
 
 namespace art {
 
-constexpr int kMaxDeg = 7;
 constexpr int kNurbsFwdBlock = 64;      // forward: one wave per (facet, group of grid rows) - no workgroup barriers
 constexpr int kNurbsBwdBlock = 512;     // backward: launch bound; 4 or 8 waves per facet (art_nurbs_bwd)
 
@@ -63,73 +62,6 @@ struct NurbsArgs {
     int grid_mode;          // 1: look for a cartesian grid (tensor-product scheme), 0: scattered scheme only
     int lds_floats;         // dynamic LDS of the launch, in floats
 };
-
-// surfaces.py:198-207 (uniform) / :209-243 (search).
-__device__ __forceinline__ int find_span(float x, const float* knots, int n, int deg, int uniform, int n_unique)
-{
-    int span;
-    if (uniform) {
-        span = (int)floorf(x * (float)(n_unique - 1)) + deg;
-    } else {
-        span = deg;
-        for (int k = deg; k < n; ++k)
-            if (x >= knots[k] && x < knots[k + 1]) { span = k; break; }
-        const float last = knots[n];
-        if (fabsf(x - last) <= 1e-5f + 1e-5f * fabsf(last)) span = n - 1;
-    }
-    // The reference would raise an IndexError outside [deg, n-1]; keep the LDS gathers in range.
-    return min(max(span, deg), n - 1);
-}
-
-// surfaces.py:294-417 for nth_derivative = 1.  DEG > 0: compile-time degree (registers);
-// DEG == 0: runtime degree `deg` (arrays may live in scratch - rare shapes only).
-template <int DEG>
-__device__ __forceinline__ void basis(float x, const float* knots, int span, int deg, float* N, float* D)
-{
-    constexpr int S = (DEG > 0 ? DEG : kMaxDeg) + 1;
-    const int pdeg = DEG > 0 ? DEG : deg;
-    float ndu[S][S], left[S], right[S];
-    ndu[0][0] = 1.0f;
-#pragma unroll
-    for (int j = 1; j < S; ++j) {
-        if (j > pdeg) break;
-        left[j] = x - knots[span + 1 - j];
-        right[j] = knots[span + j] - x;
-        float saved = 0.0f;
-#pragma unroll
-        for (int r = 0; r < S - 1; ++r) {
-            if (r >= j) break;
-            ndu[j][r] = right[r + 1] + left[j - r];
-            // (knot differences and basis values are far inside the normal range: div_noscale == '/')
-            const float tmp = div_noscale(ndu[r][j - 1], ndu[j][r]);
-            ndu[r][j] = saved + right[r + 1] * tmp;
-            saved = left[j - r] * tmp;
-        }
-        ndu[j][j] = saved;
-    }
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-        if (j > pdeg) break;
-        N[j] = ndu[j][pdeg];
-    }
-    const int pk = pdeg - 1;
-#pragma unroll
-    for (int r = 0; r < S; ++r) {
-        if (r > pdeg) break;
-        float d = 0.0f;
-        if (r >= 1) {
-            const float a0 = div_noscale(1.0f, ndu[pk + 1][r - 1]);
-            d = a0 * ndu[r - 1][pk];
-        }
-        if (r <= pk) {
-            const float a1 = div_noscale(-1.0f, ndu[pk + 1][r]);
-            d += a1 * ndu[r][pk];
-        }
-        D[r] = d * (float)pdeg;
-    }
-}
-
-__device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 
 // transforms.py:320-340.  B[0..2] = e, B[3..5] = n_ortho, B[6..8] = u.
 __device__ __forceinline__ void canting_basis(const float* cant, float* B)
@@ -469,7 +401,7 @@ __global__ __launch_bounds__(kNurbsFwdBlock) void nurbs_fwd_kernel(NurbsArgs a, 
 // Scattered scheme: one point per thread and step, 3 (p+1)(q+1) double LDS atomics per point into the facet's gradient net
 // (ds_add_f64; the order of the adds is not fixed - the sums are the same to fp32 output precision, not bit-reproducible).
 // (Round 3 merged the sums of consecutive points of a knot-span cell in registers first - 48 accumulators that set the
-// kernel's register count; the scheme now serves SurfaceGenerator.fit_nurbs only, not the epoch.)
+// kernel's register count; the scheme serves callers with non-grid points only, not the epoch.)
 // LDS: [facet tables][gradient net: ncp doubles][two basis records per working thread]
 template <int DEG>
 __device__ __forceinline__ void nurbs_bwd_scattered(const NurbsArgs& a, int hf, float* lds, const float* s_cp, const float* s_ku,
