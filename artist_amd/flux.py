@@ -14,7 +14,7 @@ from typing import Any
 import torch
 
 from . import _lib
-from .ops import _f32c, _require_cuda, _stream
+from .ops import _f32c, _require_cuda
 
 
 def target_dimensions(solar_tower, target_area_indices: torch.Tensor) -> torch.Tensor:
@@ -43,10 +43,8 @@ class FluxCrop(torch.autograd.Function):
         B, Hh, W = flux.shape
         out = torch.empty_like(flux)
         centers = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_crop_fwd(flux.data_ptr(), dims.data_ptr(), B, Hh, W, float(crop_width),
-                                              float(crop_height), out.data_ptr(), centers.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_flux_crop_fwd")
+        _lib.call("art_flux_crop_fwd", dev, flux.data_ptr(), dims.data_ptr(), B, Hh, W, float(crop_width), float(crop_height),
+                  out.data_ptr(), centers.data_ptr())
         ctx.save_for_backward(flux, dims, centers)
         ctx.crop = (float(crop_width), float(crop_height))
         return out
@@ -60,11 +58,8 @@ class FluxCrop(torch.autograd.Function):
         grad_out = _f32c(grad_out)
         grad_flux = torch.empty_like(flux)
         workspace = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_crop_bwd(flux.data_ptr(), dims.data_ptr(), centers.data_ptr(), B, Hh, W, *ctx.crop,
-                                              grad_out.data_ptr(), grad_flux.data_ptr(), workspace.data_ptr(),
-                                              _stream(dev))
-        _lib.check(rc, "art_flux_crop_bwd")
+        _lib.call("art_flux_crop_bwd", dev, flux.data_ptr(), dims.data_ptr(), centers.data_ptr(), B, Hh, W, *ctx.crop,
+                  grad_out.data_ptr(), grad_flux.data_ptr(), workspace.data_ptr())
         return grad_flux, None, None, None
 
 
@@ -89,10 +84,7 @@ class _FluxLoss(torch.autograd.Function):
         B = prediction.shape[0]
         npix = prediction.shape[1] * prediction.shape[2]
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_loss(prediction.data_ptr(), ground_truth.data_ptr(), B, npix, kind, loss.data_ptr(),
-                                          None, None, _stream(dev))
-        _lib.check(rc, "art_flux_loss")
+        _lib.call("art_flux_loss", dev, prediction.data_ptr(), ground_truth.data_ptr(), B, npix, kind, loss.data_ptr(), None, None)
         ctx.save_for_backward(prediction, ground_truth)
         ctx.kind = kind
         return loss
@@ -106,10 +98,8 @@ class _FluxLoss(torch.autograd.Function):
         npix = prediction.shape[1] * prediction.shape[2]
         grad_loss = _f32c(grad_loss)
         grad_prediction = torch.empty_like(prediction)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_loss(prediction.data_ptr(), ground_truth.data_ptr(), B, npix, ctx.kind, None,
-                                          grad_loss.data_ptr(), grad_prediction.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_flux_loss")
+        _lib.call("art_flux_loss", dev, prediction.data_ptr(), ground_truth.data_ptr(), B, npix, ctx.kind, None,
+                  grad_loss.data_ptr(), grad_prediction.data_ptr())
         return grad_prediction, None, None
 
 
@@ -138,12 +128,10 @@ class FluxCropPixelLoss(torch.autograd.Function):
         if moments is not None and (moments.shape[0] != B or moments.device != dev):
             moments = None
         FluxCropPixelLoss.calls_with_moments += moments is not None
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_crop_pixel_loss_fwd(flux.data_ptr(), dims.data_ptr(), ground_truth.data_ptr(), B, Hh, W,
-                                                         float(crop_width), float(crop_height), loss.data_ptr(), centers.data_ptr(),
-                                                         residual.data_ptr() if keep else None, unit.data_ptr() if keep else None,
-                                                         None if moments is None else moments.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_flux_crop_pixel_loss_fwd")
+        _lib.call("art_flux_crop_pixel_loss_fwd", dev, flux.data_ptr(), dims.data_ptr(), ground_truth.data_ptr(), B, Hh, W,
+                  float(crop_width), float(crop_height), loss.data_ptr(), centers.data_ptr(),
+                  residual.data_ptr() if keep else None, unit.data_ptr() if keep else None,
+                  None if moments is None else moments.data_ptr())
         if keep:
             ctx.save_for_backward(dims, centers, residual, unit)
         ctx.crop = (float(crop_width), float(crop_height))
@@ -162,11 +150,8 @@ class FluxCropPixelLoss(torch.autograd.Function):
         else:
             grad_loss = _f32c(grad_loss)
         grad_flux = torch.empty_like(residual)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_crop_pixel_loss_bwd(dims.data_ptr(), centers.data_ptr(), grad_loss.data_ptr(), stride,
-                                                         residual.data_ptr(), unit.data_ptr(), B, Hh, W, *ctx.crop, grad_flux.data_ptr(),
-                                                         _stream(dev))
-        _lib.check(rc, "art_flux_crop_pixel_loss_bwd")
+        _lib.call("art_flux_crop_pixel_loss_bwd", dev, dims.data_ptr(), centers.data_ptr(), grad_loss.data_ptr(), stride,
+                  residual.data_ptr(), unit.data_ptr(), B, Hh, W, *ctx.crop, grad_flux.data_ptr())
         return grad_flux, None, None, None, None
 
 
@@ -192,11 +177,8 @@ class FluxCropKLLoss(torch.autograd.Function):
         B, Hh, W = flux.shape
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
         record = torch.empty((B, 8), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_crop_kl_loss_fwd(flux.data_ptr(), dims.data_ptr(), ground_truth.data_ptr(), B, Hh, W,
-                                                      float(crop_width), float(crop_height), loss.data_ptr(),
-                                                      record.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_flux_crop_kl_loss_fwd")
+        _lib.call("art_flux_crop_kl_loss_fwd", dev, flux.data_ptr(), dims.data_ptr(), ground_truth.data_ptr(), B, Hh, W,
+                  float(crop_width), float(crop_height), loss.data_ptr(), record.data_ptr())
         ctx.save_for_backward(flux, dims, ground_truth, record)
         ctx.crop = (float(crop_width), float(crop_height))
         return loss
@@ -210,11 +192,8 @@ class FluxCropKLLoss(torch.autograd.Function):
         grad_loss = _f32c(grad_loss)
         grad_flux = torch.empty_like(flux)
         workspace = torch.empty((B * Hh * W + 5 * B,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_crop_kl_loss_bwd(flux.data_ptr(), dims.data_ptr(), ground_truth.data_ptr(),
-                                                      record.data_ptr(), grad_loss.data_ptr(), B, Hh, W, *ctx.crop,
-                                                      grad_flux.data_ptr(), workspace.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_flux_crop_kl_loss_bwd")
+        _lib.call("art_flux_crop_kl_loss_bwd", dev, flux.data_ptr(), dims.data_ptr(), ground_truth.data_ptr(),
+                  record.data_ptr(), grad_loss.data_ptr(), B, Hh, W, *ctx.crop, grad_flux.data_ptr(), workspace.data_ptr())
         return grad_flux, None, None, None, None
 
 
@@ -235,9 +214,7 @@ class _CenterOfMass(torch.autograd.Function):
             raise ValueError("bitmaps must be [number_of_active_heliostats, bitmap_resolution_u, bitmap_resolution_e]")
         B, Hh, W = bitmaps.shape
         com = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_center_of_mass(bitmaps.data_ptr(), B, Hh, W, com.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_flux_center_of_mass")
+        _lib.call("art_flux_center_of_mass", dev, bitmaps.data_ptr(), B, Hh, W, com.data_ptr())
         ctx.save_for_backward(com)
         ctx.shape = (B, Hh, W)
         return com[:, :2]
@@ -250,10 +227,7 @@ class _CenterOfMass(torch.autograd.Function):
         dev = com.device
         grad_com = _f32c(grad_com)
         grad = torch.empty((B, Hh, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_flux_center_of_mass_bwd(com.data_ptr(), grad_com.data_ptr(), B, Hh, W, grad.data_ptr(),
-                                                        _stream(dev))
-        _lib.check(rc, "art_flux_center_of_mass_bwd")
+        _lib.call("art_flux_center_of_mass_bwd", dev, com.data_ptr(), grad_com.data_ptr(), B, Hh, W, grad.data_ptr())
         return grad
 
 

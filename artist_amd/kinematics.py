@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .ops import _f32c, _require_cuda, _stream
+from .ops import _f32c, _require_cuda
 
 __all__ = ["RigidBody", "Actuators", "rigid_body_orientations"]
 
@@ -59,14 +59,12 @@ class RigidBodyOrientations(torch.autograd.Function):
         orientations = torch.empty((H, 4, 4), dtype=torch.float32, device=dev)
         scratch = torch.empty((H + int(max_iter) + 1,), dtype=torch.float32, device=dev)
         evaluations = torch.zeros((1,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_rigid_body_fwd(
-                mode, positions.data_ptr(), rot_dev.data_ptr(), trans_dev.data_ptr(), act_nonopt.data_ptr(), rows,
-                act_opt.data_ptr() if linear else None, offsets.data_ptr(),
-                incident.data_ptr() if mode == 1 else None, aim.data_ptr() if mode == 1 else None, H,
-                int(max_iter), float(min_eps), motor.data_ptr(), orientations.data_ptr(), scratch.data_ptr(),
-                evaluations.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_rigid_body_fwd")
+        _lib.call("art_rigid_body_fwd", dev,
+                  mode, positions.data_ptr(), rot_dev.data_ptr(), trans_dev.data_ptr(), act_nonopt.data_ptr(), rows,
+                  act_opt.data_ptr() if linear else None, offsets.data_ptr(),
+                  incident.data_ptr() if mode == 1 else None, aim.data_ptr() if mode == 1 else None, H,
+                  int(max_iter), float(min_eps), motor.data_ptr(), orientations.data_ptr(), scratch.data_ptr(),
+                  evaluations.data_ptr())
         ctx.mode, ctx.rows = mode, rows
         ctx.save_for_backward(positions, rot_dev, trans_dev, act_nonopt, act_opt, offsets,
                               incident if mode == 1 else None, aim if mode == 1 else None, motor, evaluations)
@@ -85,15 +83,13 @@ class RigidBodyOrientations(torch.autograd.Function):
         grad_trans = torch.empty_like(trans_dev)
         grad_opt = torch.empty_like(act_opt) if linear else None
         grad_motor = torch.empty_like(motor) if ctx.mode == 0 and ctx.needs_input_grad[9] else None
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_rigid_body_bwd(
-                ctx.mode, positions.data_ptr(), rot_dev.data_ptr(), trans_dev.data_ptr(), act_nonopt.data_ptr(), ctx.rows,
-                act_opt.data_ptr() if linear else None, offsets.data_ptr(),
-                incident.data_ptr() if ctx.mode == 1 else None, aim.data_ptr() if ctx.mode == 1 else None, H,
-                motor.data_ptr(), evaluations.data_ptr(), grad_orientations.data_ptr(), grad_rot.data_ptr(),
-                grad_trans.data_ptr(), grad_opt.data_ptr() if linear else None,
-                grad_motor.data_ptr() if grad_motor is not None else None, _stream(dev))
-        _lib.check(rc, "art_rigid_body_bwd")
+        _lib.call("art_rigid_body_bwd", dev,
+                  ctx.mode, positions.data_ptr(), rot_dev.data_ptr(), trans_dev.data_ptr(), act_nonopt.data_ptr(), ctx.rows,
+                  act_opt.data_ptr() if linear else None, offsets.data_ptr(),
+                  incident.data_ptr() if ctx.mode == 1 else None, aim.data_ptr() if ctx.mode == 1 else None, H,
+                  motor.data_ptr(), evaluations.data_ptr(), grad_orientations.data_ptr(), grad_rot.data_ptr(),
+                  grad_trans.data_ptr(), grad_opt.data_ptr() if linear else None,
+                  grad_motor.data_ptr() if grad_motor is not None else None)
         return None, None, grad_rot, grad_trans, None, grad_opt, None, None, None, grad_motor, None, None
 
 

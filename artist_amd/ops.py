@@ -7,7 +7,6 @@ raise.
 from __future__ import annotations
 
 import collections
-import contextlib
 import math
 
 import weakref
@@ -25,9 +24,10 @@ def _stream(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-# Measurement hook (bench.py's roofline leg, tools/): when switched on, the two trace calls are bracketed by a pair of HIP events
-# on the stream they are launched on, so a caller can read the launch durations of a region it times WITHOUT changing that region
-# (no synchronisation; two event records per call).  Off by default: None.
+# Measurement hook (bench.py's roofline leg, tools/): when switched on, the calls made through _timed_call (the trace calls, the
+# sampler, the regularisers, the surface fit) are bracketed by a pair of HIP events on the stream they are launched on, so a
+# caller can read the launch durations of a region it times WITHOUT changing that region (no synchronisation; two event records
+# per call).  Off by default: None.
 _LAUNCH_EVENTS = None
 
 
@@ -43,19 +43,20 @@ def record_launch_events(on: bool = True):
     return out
 
 
-@contextlib.contextmanager
-def _launch(name: str, device: torch.device):
+def _timed_call(name: str, device: torch.device, *args, on_error=_lib.check) -> None:
+    """``_lib.call`` for the entry points that ``record_launch_events`` times."""
     rec = _LAUNCH_EVENTS
+    if rec is None:
+        return _lib.call(name, device, *args, on_error=on_error)
+    stream = torch.cuda.current_stream(device)
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.device(device):
-        if rec is None:
-            yield
-            return
-        stream = torch.cuda.current_stream(device)
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record(stream)
-        yield
-        end.record(stream)
-        rec.setdefault(name, []).append((start, end))
+        try:
+            _lib.call(name, device, *args, on_error=on_error)
+        finally:                                   # (a call that reports an error is recorded like any other)
+            end.record(stream)
+            rec.setdefault(name, []).append((start, end))
 
 
 def _require_cuda(*tensors: torch.Tensor) -> torch.device:
@@ -174,9 +175,7 @@ def reflect_directions(incident: torch.Tensor, normals: torch.Tensor) -> torch.T
     if incident.shape != (H, 4) or normals.shape != (H, P, 4):
         raise ValueError("incident must be [H,4] and normals [H,P,4]")
     out = torch.empty_like(normals)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().art_reflect(incident.data_ptr(), normals.data_ptr(), H, P, out.data_ptr(), _stream(dev))
-    _lib.check(rc, "art_reflect")
+    _lib.call("art_reflect", dev, incident.data_ptr(), normals.data_ptr(), H, P, out.data_ptr())
     return out
 
 
@@ -208,10 +207,7 @@ def sample_distortions(rows, number_of_rays: int, number_of_points: int, seed: i
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed as a 64-bit two's-complement value
     seed = seed - (1 << 64) if seed >= (1 << 63) else seed
     out = torch.empty((n, R, P, 2), dtype=torch.float32, device=dev)
-    with _launch("art_sample_distortions", dev):
-        rc = _lib.lib().art_sample_distortions(int(seed), rows_t.data_ptr(), n, R, P, lu, le, l00, l10, l11, out.data_ptr(),
-                                               _stream(dev))
-    _lib.check(rc, "art_sample_distortions")
+    _timed_call("art_sample_distortions", dev, int(seed), rows_t.data_ptr(), n, R, P, lu, le, l00, l10, l11, out.data_ptr())
     return out
 
 
@@ -229,16 +225,29 @@ def check_async_errors(device=None, clear: bool = True) -> None:
         # so wait for the whole device, not only for the current stream
         torch.cuda.synchronize(dev)
         rc = _lib.lib().art_async_status(_stream(dev), 1 if clear else 0)
-    if rc == -2:
-        _ACCUM.clear()              # a skipped heliostat leaves nothing behind, but take no chances with the invariant
-        raise IndexError("target_area_indices out of range (found by the kernels: art_async_status)")
-    if rc == -5:
-        raise _lib.ArtistHipError(f"a heliostat has more blocking rectangles inside its ray cone than its candidate row holds "
-                                  f"(artist_amd.ops.BLOCKING_CANDIDATES = {BLOCKING_CANDIDATES}: raise it, or None for no bound; "
-                                  "found by art_blocking_filter: art_async_status); its blocking would be incomplete")
-    if rc == -6:
-        _ACCUM.clear()              # (a launch that ended abnormally may have left pixel accumulators behind)
-    _lib.check(rc, "art_async_status")
+    if rc != _lib.ART_OK:
+        _raise_status(rc, "art_async_status")
+
+
+def _raise_status(code: int, what: str) -> None:
+    """The exception for a non-zero ``code`` of ``what`` = art_trace_fwd, art_trace_bwd or art_async_status: the sticky status
+    of the device (include/artist_hip.h), which the trace calls return at once for as long as it is set, or the call's own
+    error."""
+    # The pixel accumulators must be all zero when a trace starts.  A skipped heliostat leaves nothing behind, but take no
+    # chances with the invariant; a launch that ended abnormally (ART_EQUEUE) may have left some.  A forward call that
+    # refused or failed drops them whatever the code; the backward call does not use them.
+    if what == "art_trace_fwd" or (what == "art_async_status" and code in (_lib.ART_ETARGET, _lib.ART_EQUEUE)):
+        _ACCUM.clear()
+    if code == _lib.ART_ETARGET:
+        raise IndexError(f"target_area_indices out of range (found by the kernels, reported by {what}; "
+                         "artist_amd.ops.check_async_errors() clears the status)")
+    if code == _lib.ART_ECANDIDATES:
+        raise _lib.ArtistHipError(
+            f"a heliostat has more blocking rectangles inside its ray cone than its candidate row holds "
+            f"(artist_amd.ops.BLOCKING_CANDIDATES = {BLOCKING_CANDIDATES}: raise it, or set it to None for no bound; found by "
+            f"art_blocking_filter, reported by {what}): its blocking is incomplete, and its bitmaps and factors are NaN; "
+            "artist_amd.ops.check_async_errors() clears the status")
+    _lib.check(code, what)
 
 
 # Centre-of-mass sums that came with a traced bitmap tensor: data pointer -> (weak reference to the tensor object, sums).  An
@@ -312,12 +321,9 @@ class TraceRays(torch.autograd.Function):
             cand = torch.empty((H, Cmax), dtype=torch.int32, device=dev)
             cand_count = torch.empty((H,), dtype=torch.int32, device=dev)
             workspace = torch.empty((int(_lib.lib().art_blocking_workspace_bytes(H, N)),), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = _lib.lib().art_blocking_filter(
-                    *geometry, float(ray_magnitude), H, R, P, T, Tc, width, height, prim_corners.data_ptr(),
-                    owner.data_ptr(), N, float(max_scatter_angle), 1 if lbvh_compat else 0, Cmax, flags.data_ptr(),
-                    cand.data_ptr(), cand_count.data_ptr(), workspace.data_ptr(), _stream(dev))
-            _lib.check(rc, "art_blocking_filter")
+            _lib.call("art_blocking_filter", dev, *geometry, float(ray_magnitude), H, R, P, T, Tc, width, height,
+                      prim_corners.data_ptr(), owner.data_ptr(), N, float(max_scatter_angle), 1 if lbvh_compat else 0, Cmax,
+                      flags.data_ptr(), cand.data_ptr(), cand_count.data_ptr(), workspace.data_ptr())
             # (more than Cmax rectangles inside a heliostat's ray cone: the device reports it - ART_ECANDIDATES from
             #  check_async_errors() or from the next trace call - instead of a host read of the counts in every call)
             block_tabs = (prim_corners, prim_spans, prim_normals, cand, cand_count)
@@ -333,24 +339,10 @@ class TraceRays(torch.autograd.Function):
         moments = None
         if height >= 4 and (height * width) % 2 == 0 and 0 < n_maps <= 65535:
             moments = torch.empty((n_maps, 4, 3), dtype=torch.float64, device=dev)
-        with _launch("art_trace_fwd", dev):
-            rc = _lib.lib().art_trace_fwd(
-                *geometry, *block_ptrs, Cmax, float(max_scatter_angle), float(ray_magnitude), float(extinction),
-                float(reflectivity),
-                H, R, P, points_per_facet, T, Tc, width, height, 1 if per_target else 0, flux.data_ptr(), factors.data_ptr(),
-                accum.data_ptr(), None if moments is None else moments.data_ptr(), _stream(dev))
-        if rc != 0:
-            _ACCUM.clear()
-        if rc == -2:
-            raise IndexError("target_area_indices out of range (found by the kernels of an earlier call; "
-                             "artist_amd.ops.check_async_errors() clears the status)")
-        if rc == -5:
-            raise _lib.ArtistHipError(
-                f"a heliostat has more blocking rectangles inside its ray cone than its candidate row holds "
-                f"(artist_amd.ops.BLOCKING_CANDIDATES = {BLOCKING_CANDIDATES}: raise it, or set it to None; found by "
-                "art_blocking_filter in an earlier call, whose bitmaps and factors for that heliostat are NaN; "
-                "artist_amd.ops.check_async_errors() clears the status)")
-        _lib.check(rc, "art_trace_fwd")
+        _timed_call("art_trace_fwd", dev, *geometry, *block_ptrs, Cmax, float(max_scatter_angle), float(ray_magnitude),
+                    float(extinction), float(reflectivity), H, R, P, points_per_facet, T, Tc, width, height, 1 if per_target else 0,
+                    flux.data_ptr(), factors.data_ptr(), accum.data_ptr(), None if moments is None else moments.data_ptr(),
+                    on_error=_raise_status)
         ctx.save_for_backward(origins, normals, incident, dist_u, dist_e, target_idx, centers, plane_normals, dims,
                               *cyl_tabs, *block_tabs)
         ctx.n_cyl = len(cyl_tabs)
@@ -389,18 +381,13 @@ class TraceRays(torch.autograd.Function):
             g_pc, g_ps, g_pn = (torch.empty_like(t) for t in block_tabs[:3])
         n_scratch = int(_lib.lib().art_trace_bwd_scratch_floats(H, R, P, points_per_facet, Cmax if block_tabs else 0))
         scratch = torch.empty((n_scratch,), dtype=torch.float32, device=dev) if n_scratch else None
-        with _launch("art_trace_bwd", dev):
-            rc = _lib.lib().art_trace_bwd(
-                origins.data_ptr(), normals.data_ptr(), incident.data_ptr(), dist_u.data_ptr(), dist_e.data_ptr(),
-                sh, sr, sp, target_idx.data_ptr(), *_planar_ptrs(centers, plane_normals, dims), *cyl_ptrs,
-                *block_ptrs, Cmax, N, max_scatter, mag, ext, refl, H, R, P, points_per_facet, centers.shape[0], Tc, width, height,
-                1 if per_target else 0, grad_flux.data_ptr(), g_o.data_ptr(), g_n.data_ptr(),
-                *(t.data_ptr() if t is not None else None for t in (g_pc, g_ps, g_pn)),
-                None if scratch is None else scratch.data_ptr(), n_scratch, _stream(dev))
-        if rc == -2:
-            raise IndexError("target_area_indices out of range (found by the kernels of an earlier call; "
-                             "artist_amd.ops.check_async_errors() clears the status)")
-        _lib.check(rc, "art_trace_bwd")
+        _timed_call("art_trace_bwd", dev,
+                    origins.data_ptr(), normals.data_ptr(), incident.data_ptr(), dist_u.data_ptr(), dist_e.data_ptr(),
+                    sh, sr, sp, target_idx.data_ptr(), *_planar_ptrs(centers, plane_normals, dims), *cyl_ptrs,
+                    *block_ptrs, Cmax, N, max_scatter, mag, ext, refl, H, R, P, points_per_facet, centers.shape[0], Tc, width, height,
+                    1 if per_target else 0, grad_flux.data_ptr(), g_o.data_ptr(), g_n.data_ptr(),
+                    *(t.data_ptr() if t is not None else None for t in (g_pc, g_ps, g_pn)),
+                    None if scratch is None else scratch.data_ptr(), n_scratch, on_error=_raise_status)
         return (g_o, g_n) + (None,) * 14 + (g_pc, g_ps, g_pn, None, None, None, None)
 
 
@@ -442,10 +429,7 @@ class _PerTargetSum(torch.autograd.Function):
         H = b.shape[0]
         npix = int(math.prod(b.shape[1:]))
         out = torch.empty((n_targets,) + tuple(b.shape[1:]), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_per_target_sum(b.data_ptr(), target_idx.data_ptr(), H, n_targets, npix,
-                                               out.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_per_target_sum")
+        _lib.call("art_per_target_sum", dev, b.data_ptr(), target_idx.data_ptr(), H, n_targets, npix, out.data_ptr())
         ctx.save_for_backward(target_idx)
         ctx.n_targets = n_targets
         return out
@@ -488,13 +472,11 @@ class NurbsEval(torch.autograd.Function):
             ori = _f32c(orientation.detach())
             if ori.shape != (H, 4, 4) or ori.device != dev:
                 raise ValueError("orientation must be [H,4,4] on the control points' device")
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_nurbs_fwd(
-                cp.data_ptr(), uv.data_ptr(), uv.stride(0), uv.stride(1), ku.data_ptr(), kv.data_ptr(),
-                None if cant is None else cant.data_ptr(), None if tr is None else tr.data_ptr(),
-                p, q, 1 if uniform else 0, n_unique_u, n_unique_v, H, F, M, nu, nv,
-                None if ori is None else ori.data_ptr(), points.data_ptr(), normals.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_nurbs_fwd")
+        _lib.call("art_nurbs_fwd", dev,
+                  cp.data_ptr(), uv.data_ptr(), uv.stride(0), uv.stride(1), ku.data_ptr(), kv.data_ptr(),
+                  None if cant is None else cant.data_ptr(), None if tr is None else tr.data_ptr(),
+                  p, q, 1 if uniform else 0, n_unique_u, n_unique_v, H, F, M, nu, nv,
+                  None if ori is None else ori.data_ptr(), points.data_ptr(), normals.data_ptr())
         ctx.save_for_backward(cp, uv, ku, kv, cant if cant is not None else cp.new_empty(0),
                               ori if ori is not None else cp.new_empty(0))
         ctx.meta = (p, q, bool(uniform), n_unique_u, n_unique_v, cant is not None, ori is not None)
@@ -510,13 +492,10 @@ class NurbsEval(torch.autograd.Function):
         M = uv.shape[2]
         g_points, g_normals = _f32c(g_points), _f32c(g_normals)
         g_cp = torch.empty_like(cp)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_nurbs_bwd(
-                cp.data_ptr(), uv.data_ptr(), uv.stride(0), uv.stride(1), ku.data_ptr(), kv.data_ptr(),
-                cant.data_ptr() if has_cant else None, p, q, 1 if uniform else 0, nuq_u, nuq_v, H, F, M, nu, nv,
-                ori.data_ptr() if has_ori else None, g_points.data_ptr(), g_normals.data_ptr(), g_cp.data_ptr(),
-                _stream(dev))
-        _lib.check(rc, "art_nurbs_bwd")
+        _lib.call("art_nurbs_bwd", dev,
+                  cp.data_ptr(), uv.data_ptr(), uv.stride(0), uv.stride(1), ku.data_ptr(), kv.data_ptr(),
+                  cant.data_ptr() if has_cant else None, p, q, 1 if uniform else 0, nuq_u, nuq_v, H, F, M, nu, nv,
+                  ori.data_ptr() if has_ori else None, g_points.data_ptr(), g_normals.data_ptr(), g_cp.data_ptr())
         return (g_cp,) + (None,) * 11
 
 
@@ -542,10 +521,8 @@ class AlignSurfaces(torch.autograd.Function):
         if points.shape != (H, P, 4) or normals.shape != (H, P, 4) or orientation.shape != (H, 4, 4):
             raise ValueError("points/normals must be [H,P,4] and orientation [H,4,4]")
         out_p, out_n = torch.empty_like(points), torch.empty_like(normals)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_align_fwd(points.data_ptr(), normals.data_ptr(), orientation.data_ptr(), H, P,
-                                          out_p.data_ptr(), out_n.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_align_fwd")
+        _lib.call("art_align_fwd", dev, points.data_ptr(), normals.data_ptr(), orientation.data_ptr(), H, P,
+                  out_p.data_ptr(), out_n.data_ptr())
         ctx.save_for_backward(points, normals, orientation)
         return out_p, out_n
 
@@ -558,11 +535,9 @@ class AlignSurfaces(torch.autograd.Function):
         g_out_p, g_out_n = _f32c(g_out_p), _f32c(g_out_n)
         g_p, g_n = torch.empty_like(points), torch.empty_like(normals)
         g_m = torch.empty_like(orientation) if ctx.needs_input_grad[2] else None
-        with torch.cuda.device(dev):
-            rc = _lib.lib().art_align_bwd(points.data_ptr(), normals.data_ptr(), orientation.data_ptr(),
-                                          g_out_p.data_ptr(), g_out_n.data_ptr(), H, P, g_p.data_ptr(), g_n.data_ptr(),
-                                          None if g_m is None else g_m.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_align_bwd")
+        _lib.call("art_align_bwd", dev, points.data_ptr(), normals.data_ptr(), orientation.data_ptr(),
+                  g_out_p.data_ptr(), g_out_n.data_ptr(), H, P, g_p.data_ptr(), g_n.data_ptr(),
+                  None if g_m is None else g_m.data_ptr())
         return g_p, g_n, g_m
 
 

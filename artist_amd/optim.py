@@ -40,7 +40,6 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.lib()
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             for p in group["params"]:
@@ -66,10 +65,7 @@ class Adam(torch.optim.Optimizer):
                     if p.dim() < 3 or p.shape[-1] != 3:
                         raise ValueError("lock_outer_edges needs parameters shaped [..., nu, nv, 3]")
                     nu, nv = int(p.shape[-3]), int(p.shape[-2])
-                with torch.cuda.device(p.device):
-                    rc = lib.art_adam_step(p.data_ptr(), grad.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
-                                           p.numel(), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                           float(group["weight_decay"]), state["step"], 1 if group["maximize"] else 0, nu, nv,
-                                           torch.cuda.current_stream(p.device).cuda_stream)
-                _lib.check(rc, "art_adam_step")
+                _lib.call("art_adam_step", p.device, p.data_ptr(), grad.data_ptr(), state["exp_avg"].data_ptr(),
+                          state["exp_avg_sq"].data_ptr(), p.numel(), float(group["lr"]), float(beta1), float(beta2),
+                          float(group["eps"]), float(group["weight_decay"]), state["step"], 1 if group["maximize"] else 0, nu, nv)
         return loss

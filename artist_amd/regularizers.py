@@ -12,8 +12,7 @@ from typing import Any
 
 import torch
 
-from . import _lib
-from .ops import _f32c, _launch, _require_cuda, _stream
+from .ops import _f32c, _require_cuda, _timed_call
 
 __all__ = ["Regularizer", "SmoothnessRegularizer", "IdealSurfaceRegularizer", "SurfaceRegularizers", "surface_regularizers",
            "surface_regularization_terms"]
@@ -46,11 +45,8 @@ class SurfaceRegularizers(torch.autograd.Function):
         out_s = current.new_empty((H, F) if smoothness else (0,))
         out_i = current.new_empty((H, F) if ideal else (0,))
         if N > 0 and (smoothness or ideal):
-            with _launch("art_surface_regularizers_fwd", dev):
-                rc = _lib.lib().art_surface_regularizers_fwd(current.data_ptr(), original.data_ptr(), N, U, V,
-                                                             out_s.data_ptr() if smoothness else None,
-                                                             out_i.data_ptr() if ideal else None, _stream(dev))
-            _lib.check(rc, "art_surface_regularizers_fwd")
+            _timed_call("art_surface_regularizers_fwd", dev, current.data_ptr(), original.data_ptr(), N, U, V,
+                        out_s.data_ptr() if smoothness else None, out_i.data_ptr() if ideal else None)
         ctx.save_for_backward(current, original)
         ctx.set_materialize_grads(False)
         if not smoothness:
@@ -73,11 +69,8 @@ class SurfaceRegularizers(torch.autograd.Function):
         gi = None if grad_i is None or grad_i.numel() == 0 else _f32c(grad_i)
         g = torch.empty_like(current)
         if N > 0:
-            with _launch("art_surface_regularizers_bwd", dev):
-                rc = _lib.lib().art_surface_regularizers_bwd(current.data_ptr(), original.data_ptr(), N, U, V,
-                                                             None if gs is None else gs.data_ptr(),
-                                                             None if gi is None else gi.data_ptr(), g.data_ptr(), _stream(dev))
-            _lib.check(rc, "art_surface_regularizers_bwd")
+            _timed_call("art_surface_regularizers_bwd", dev, current.data_ptr(), original.data_ptr(), N, U, V,
+                        None if gs is None else gs.data_ptr(), None if gi is None else gi.data_ptr(), g.data_ptr())
         return (g if need_cur else None), (-g if need_org else None), None, None
 
 

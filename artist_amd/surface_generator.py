@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .nurbs import NURBSSurfaces, create_planar_nurbs_control_points
-from .ops import _f32c, _launch, _require_cuda, _stream
+from .ops import _f32c, _require_cuda, _timed_call
 from .optim import Adam as _HipAdam
 
 __all__ = ["SurfaceGenerator", "FittedFacet", "FIT_NURBS_FROM_POINTS", "FIT_NURBS_FROM_NORMALS"]
@@ -102,8 +102,7 @@ class _Prepared:
             if n_valid.shape != (self.B,):
                 raise ValueError(f"n_valid must be [B] = [{self.B}], got {tuple(n_valid.shape)}")
         self.n_valid = n_valid
-        lib = _lib.lib()
-        W = int(lib.art_surface_fit_table_words(p, q))
+        W = int(_lib.lib().art_surface_fit_table_words(p, q))
         if W < 0:
             raise ValueError(f"NURBS degrees must be in 1..7, got ({p}, {q})")
         ncells = (nu - p) * (nv - q)
@@ -112,12 +111,9 @@ class _Prepared:
         self.perm = torch.empty((self.B, self.N), dtype=torch.int32, device=dev)
         self.cell_start = torch.empty((self.B, max(ncells, 0) + 1), dtype=torch.int32, device=dev)
         self.table = torch.empty((self.B, self.N, W), dtype=torch.float32, device=dev)
-        with _launch("art_surface_fit_prepare", dev):
-            rc = lib.art_surface_fit_prepare(self.points.data_ptr(), None if n_valid is None else n_valid.data_ptr(),
-                                             knots_u.data_ptr(), knots_v.data_ptr(), self.B, self.N, nu, nv, p, q,
-                                             self.eval_uv.data_ptr(), self.initial_control_points.data_ptr(), self.perm.data_ptr(),
-                                             self.cell_start.data_ptr(), self.table.data_ptr(), _stream(dev))
-        _lib.check(rc, "art_surface_fit_prepare")
+        _timed_call("art_surface_fit_prepare", dev, self.points.data_ptr(), self._nv_ptr(), knots_u.data_ptr(), knots_v.data_ptr(),
+                    self.B, self.N, nu, nv, p, q, self.eval_uv.data_ptr(), self.initial_control_points.data_ptr(), self.perm.data_ptr(),
+                    self.cell_start.data_ptr(), self.table.data_ptr())
 
     def _nv_ptr(self):
         return None if self.n_valid is None else self.n_valid.data_ptr()
@@ -129,13 +125,9 @@ class _Prepared:
         grad = torch.empty_like(cp)
         pts = torch.zeros((self.B, self.N, 4), dtype=torch.float32, device=self.device) if with_points else None
         nrm = torch.zeros_like(pts) if with_points else None
-        with _launch("art_surface_fit_loss_grad", self.device):
-            rc = _lib.lib().art_surface_fit_loss_grad(cp.data_ptr(), targets.data_ptr(), self._nv_ptr(), self.perm.data_ptr(),
-                                                      self.cell_start.data_ptr(), self.table.data_ptr(), self.B, self.N, self.nu,
-                                                      self.nv, self.p, self.q, method, loss.data_ptr(), grad.data_ptr(),
-                                                      None if pts is None else pts.data_ptr(),
-                                                      None if nrm is None else nrm.data_ptr(), _stream(self.device))
-        _lib.check(rc, "art_surface_fit_loss_grad")
+        _timed_call("art_surface_fit_loss_grad", self.device, cp.data_ptr(), targets.data_ptr(), self._nv_ptr(), self.perm.data_ptr(),
+                    self.cell_start.data_ptr(), self.table.data_ptr(), self.B, self.N, self.nu, self.nv, self.p, self.q, method,
+                    loss.data_ptr(), grad.data_ptr(), None if pts is None else pts.data_ptr(), None if nrm is None else nrm.data_ptr())
         return (loss, grad, pts, nrm) if with_points else (loss, grad)
 
 
@@ -170,20 +162,16 @@ class _FitState:
 def run_epochs(prep: _Prepared, state: _FitState, targets: torch.Tensor, method: int, epochs: int, tolerance: float,
                max_epoch: int, adam: dict, sched: dict) -> None:
     """``epochs`` epochs on every facet that has not stopped, in launches of at most 1024 epochs."""
-    lib = _lib.lib()
-    dev = prep.device
     while epochs > 0:
         chunk = min(epochs, _MAX_EPOCHS_PER_LAUNCH)
-        with _launch("art_surface_fit_run", dev):
-            rc = lib.art_surface_fit_run(
-                state.control_points.data_ptr(), state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.f64.data_ptr(),
-                state.i32.data_ptr(), state.last_loss.data_ptr(), targets.data_ptr(), prep._nv_ptr(), prep.perm.data_ptr(),
-                prep.cell_start.data_ptr(), prep.table.data_ptr(), prep.B, prep.N, prep.nu, prep.nv, prep.p, prep.q, method,
-                chunk, float(tolerance), int(max_epoch), adam["betas"][0], adam["betas"][1], adam["eps"], adam["weight_decay"],
-                1 if adam["maximize"] else 0, 1 if sched["use"] else 0, 1 if sched["mode_max"] else 0, sched["factor"],
-                sched["patience"], sched["threshold"], 1 if sched["threshold_abs"] else 0, sched["cooldown"], sched["min_lr"],
-                sched["eps"], _stream(dev))
-        _lib.check(rc, "art_surface_fit_run")
+        _timed_call("art_surface_fit_run", prep.device,
+                    state.control_points.data_ptr(), state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.f64.data_ptr(),
+                    state.i32.data_ptr(), state.last_loss.data_ptr(), targets.data_ptr(), prep._nv_ptr(), prep.perm.data_ptr(),
+                    prep.cell_start.data_ptr(), prep.table.data_ptr(), prep.B, prep.N, prep.nu, prep.nv, prep.p, prep.q, method,
+                    chunk, float(tolerance), int(max_epoch), adam["betas"][0], adam["betas"][1], adam["eps"], adam["weight_decay"],
+                    1 if adam["maximize"] else 0, 1 if sched["use"] else 0, 1 if sched["mode_max"] else 0, sched["factor"],
+                    sched["patience"], sched["threshold"], 1 if sched["threshold_abs"] else 0, sched["cooldown"], sched["min_lr"],
+                    sched["eps"])
         epochs -= chunk
 
 

@@ -1,5 +1,5 @@
-"""CPU suite: the drop-in boundary.  The C-ABI library loads, exports exactly what include/artist_hip.h
-declares, the Python binding mirrors it, the product never touches the oracle, and it fails loudly - no
+"""CPU suite: the drop-in boundary.  The C-ABI library loads, exports exactly what the headers under include/ declare, the
+Python binding mirrors them name by name and type by type, the product never touches the oracle, and it fails loudly - no
 CPU fallback - when asked to compute without a GPU."""
 import ctypes
 import pathlib
@@ -10,44 +10,77 @@ import torch
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 
-
-def header_functions():
-    text = (ROOT / "include" / "artist_hip.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(art_[a-z_0-9]+)\s*\(", text)))
-
-
-def test_header_declares_the_expected_entry_points():
-    assert header_functions() == sorted([
+# The entry points each header is expected to declare, pinned here so that one cannot come or go unnoticed.
+EXPECTED = {
+    "artist_hip.h": [
         "art_abi_version", "art_last_hip_error", "art_strerror", "art_trace_fwd", "art_trace_bwd",
         "art_per_target_sum", "art_nurbs_fwd", "art_nurbs_bwd", "art_align_fwd", "art_align_bwd", "art_reflect",
         "art_blocking_filter", "art_blocking_workspace_bytes", "art_flux_crop_fwd", "art_flux_crop_bwd",
         "art_flux_loss", "art_rigid_body_fwd", "art_rigid_body_bwd", "art_async_status", "art_trace_bwd_scratch_floats",
         "art_trace_bwd_scratch_need", "art_adam_step",
         "art_flux_crop_pixel_loss_fwd", "art_flux_crop_pixel_loss_bwd", "art_flux_crop_kl_loss_fwd",
-        "art_flux_crop_kl_loss_bwd", "art_flux_center_of_mass", "art_flux_center_of_mass_bwd"])
+        "art_flux_crop_kl_loss_bwd", "art_flux_center_of_mass", "art_flux_center_of_mass_bwd"],
+    "artist_hip_sampler.h": ["art_sample_distortions"],
+    "artist_hip_regularizers.h": ["art_surface_regularizers_fwd", "art_surface_regularizers_bwd"],
+    "artist_hip_surface_fit.h": ["art_surface_fit_table_words", "art_surface_fit_prepare", "art_surface_fit_loss_grad",
+                                 "art_surface_fit_run"],
+}
+HEADERS = sorted(path.name for path in (ROOT / "include").glob("*.h"))
+
+# C type -> ctypes type, by kind: every pointer travels as c_void_p; a pointer is a return type only as `const char *`
+PARAMETER_KINDS = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float}
+RETURN_KINDS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
 
 
-def test_library_exports_every_declared_symbol():
+def header_text(header):
+    return re.sub(r"/\*.*?\*/", "", (ROOT / "include" / header).read_text(), flags=re.S)
+
+
+def header_functions(header="artist_hip.h"):
+    return sorted(set(re.findall(r"\b(art_[a-z_0-9]+)\s*\(", header_text(header))))
+
+
+def header_prototypes(header):
+    """name -> (restype, [argtypes]) as the header declares them, in ctypes terms."""
+    protos = {}
+    for ret, name, params in re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*(art_\w+)\s*\(([^)]*)\)\s*;", header_text(header), flags=re.M):
+        # a parameter without a star is "[const] type name"
+        argtypes = [ctypes.c_void_p if "*" in param else PARAMETER_KINDS[" ".join(w for w in param.split()[:-1] if w != "const")]
+                    for param in ([] if params.strip() in ("", "void") else params.split(","))]
+        assert name not in protos, name
+        protos[name] = (RETURN_KINDS[" ".join(ret.replace("*", " * ").split())], argtypes)
+    return protos
+
+
+def test_header_declares_the_expected_entry_points():
+    assert header_functions() == sorted(EXPECTED["artist_hip.h"])
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_binding_mirrors_the_header(header):
+    """Names, exports, and - by kind - every parameter and return type: an ``int`` bound where the header says ``int64_t``, or a
+    pointer where it says ``double``, corrupts arguments on the way to the device instead of raising."""
     from artist_amd import _lib
-    handle = ctypes.CDLL(str(_lib.LIB_PATH))
-    for name in header_functions():
-        assert hasattr(handle, name), f"{name} missing from {_lib.LIB_PATH}"
-    assert sorted(_lib.SIGNATURES) == header_functions()
+    assert sorted(_lib.HEADERS) == HEADERS == sorted(EXPECTED)
+    assert sum(len(names) for names in _lib.HEADERS.values()) == len(_lib.SIGNATURES)          # no name under two headers
+    assert {name for names in _lib.HEADERS.values() for name in names} == set(_lib.SIGNATURES)
+    protos = header_prototypes(header)
+    assert sorted(protos) == header_functions(header) == sorted(_lib.HEADERS[header]) == sorted(EXPECTED[header])
+    exported = ctypes.CDLL(str(_lib.LIB_PATH))
     lib = _lib.lib()                       # no compute call: loading + version query only
+    for name, (restype, argtypes) in protos.items():
+        assert hasattr(exported, name), f"{name} missing from {_lib.LIB_PATH}"
+        assert _lib.SIGNATURES[name] == (restype, argtypes), name
+        bound = getattr(lib, name)
+        assert (bound.restype, list(bound.argtypes)) == (restype, argtypes), name
+    # the return codes: every ART_OK / ART_E* the headers define, with the header's value
+    defines = {name: int(value) for h in HEADERS
+               for name, value in re.findall(r"^#define (ART_OK|ART_E\w+) (-?\d+)", header_text(h), flags=re.M)}
+    assert defines == {name: value for name, value in vars(_lib).items() if name == "ART_OK" or name.startswith("ART_E")}
+    assert sorted(defines) == sorted(["ART_OK", "ART_EINVAL", "ART_ETARGET", "ART_ELAUNCH", "ART_EUNSUPPORTED", "ART_ECANDIDATES",
+                                      "ART_EQUEUE"])
     assert lib.art_abi_version() == _lib.ABI_VERSION
-    assert lib.art_strerror(0) == b"ok" and b"invalid" in lib.art_strerror(-1)
-
-
-def test_argument_counts_match_the_header():
-    from artist_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "artist_hip.h").read_text(), flags=re.S)
-    for name, argtypes in _lib.SIGNATURES.items():
-        m = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, text, flags=re.S)
-        assert m, name
-        params = m.group(1).strip()
-        n_params = 0 if params in ("", "void") else params.count(",") + 1
-        assert n_params == len(argtypes), (name, n_params, len(argtypes))
+    assert lib.art_strerror(_lib.ART_OK) == b"ok" and b"invalid" in lib.art_strerror(_lib.ART_EINVAL)
 
 
 def test_product_does_not_touch_the_oracle():

@@ -2,8 +2,6 @@
 reference's own runs (tests/golden/surface_fit_*.npz) - it is the yardstick the GPU tests carry -, and the argument handling of
 ``artist_amd.SurfaceGenerator`` is checked."""
 import math
-import pathlib
-import re
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import torch
 
 import surface_fit_ref as sfr
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
 CASES = [(n, net, deg, method) for n in (37, 800) for net, deg in ((5, 2), (10, 3)) for method in (sfr.POINTS, sfr.NORMALS)]
 PLATEAU = dict(factor=0.2, patience=5, threshold=1e-7, threshold_mode="abs")
 MARGIN = 3.0            # the margin of tests/test_gpu_optimizer_epoch.py over the reference's own fp32-vs-fp64 distance
@@ -30,16 +27,6 @@ def test_surface_generator_is_exported():
     assert gen._n_cp == (10, 10) and gen._deg == (3, 3)
     for name in ("fit_nurbs", "fit_nurbs_batch", "generate_fitted_surface_config", "generate_ideal_surface_config"):
         assert callable(getattr(gen, name))
-
-
-def test_binding_mirrors_the_header():
-    from artist_amd import _lib
-    header = (ROOT / "include" / "artist_hip_surface_fit.h").read_text()
-    protos = dict(re.findall(r"^(?:int|int64_t) (art_\w+)\(([^;]*)\);", header, flags=re.M | re.S))
-    assert set(protos) == set(_lib.SURFACE_FIT_SIGNATURES)
-    for name, args in protos.items():
-        assert len([a for a in args.split(",") if a.strip()]) == len(_lib.SURFACE_FIT_SIGNATURES[name]), name
-    assert "surface_fit_kernels.o" in (ROOT / "artist_amd" / "csrc" / "Makefile").read_text()
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: case_name(*c))

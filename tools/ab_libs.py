@@ -61,13 +61,7 @@ def main():
         env = dict(x.split("=", 1) for x in parts if "=" in x)
         handle = default
         if path:
-            handle = ctypes.CDLL(str(pathlib.Path(path).resolve()))
-            for fname, argtypes in _lib.SIGNATURES.items():
-                fn = getattr(handle, fname)
-                fn.argtypes = argtypes
-                fn.restype = (ctypes.c_char_p if fname == "art_strerror"
-                              else ctypes.c_int64 if fname in ("art_blocking_workspace_bytes", "art_trace_bwd_scratch_floats") else ctypes.c_int)
-            assert handle.art_abi_version() == _lib.ABI_VERSION, (path, handle.art_abi_version())
+            handle = _lib.bind(ctypes.CDLL(str(pathlib.Path(path).resolve())), path)
         variants.append((name, handle, env))
 
     def run(handle, env, what):
