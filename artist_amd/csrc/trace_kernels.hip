@@ -1009,6 +1009,19 @@ __device__ __forceinline__ float select_mask(unsigned long long mask, float a, f
 __device__ __forceinline__ unsigned f32_bits(float x) { return __builtin_bit_cast(unsigned, x); }
 __device__ __forceinline__ unsigned long long ballot64(bool c) { return __builtin_amdgcn_ballot_w64(c); }
 
+// One step of the lean bodies' distortion ring (DEPTH slots su<j>, se<j>; `request`, `trace_one`, `k` and `nr` are the
+// caller's): the slot's value moves to registers of its own first, so that the new request can land in the SAME registers -
+// otherwise the slots rotate and the loop's back-edge has to copy (= wait for) all of them.  A ray's arithmetic stays inside
+// its step: hoisting the next step's head above it made the compiler spill the ray's live values around the hoisted code.
+#define ART_RING_STEP(j, DEPTH)                                                     \
+            {                                                                       \
+                float u, e;                                                         \
+                asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(u), "=v"(e) : "v"(su##j), "v"(se##j) : "memory"); \
+                request(k + j + DEPTH, su##j, se##j);                               \
+                trace_one(u, e, k + j < nr ? ~0ull : 0ull);                         \
+                __builtin_amdgcn_sched_barrier(0);                                  \
+            }
+
 constexpr int kLeanFwdPoints = 2560;   // points per item of the lean forward kernel when the facet structure is known
 constexpr int kPackTrips = 4;          // a block whose edge points are packed holds at most this many trips of points
 constexpr int kPackPoints = 2560;      // ... and this many points (room for the permutation)
@@ -1345,25 +1358,12 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
             request(2, su2, se2); request(3, su3, se3);
             request(4, su4, se4); request(5, su5, se5);
             request(6, su6, se6); request(7, su7, se7);
-#define ART_RING_STEP(j)                                                            \
-            {                                                                       \
-                /* the slot's value moves to registers of its own first, so that the new request can land in the */ \
-                /* SAME registers: otherwise the slots rotate and the loop's back-edge has to copy (= wait for) all of them */ \
-                float u, e;                                                         \
-                asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(u), "=v"(e) : "v"(su##j), "v"(se##j) : "memory"); \
-                request(k + j + 8, su##j, se##j);                      \
-                trace_one(u, e, k + j < nr ? ~0ull : 0ull);                          \
-                /* a ray's arithmetic stays inside its step: hoisting the next step's head above it made the */ \
-                /* compiler spill the ray's live values around the hoisted code */   \
-                __builtin_amdgcn_sched_barrier(0);                                  \
-            }
             for (int k = 0; k < nr; k += 8) {
-                ART_RING_STEP(0) ART_RING_STEP(1)
-                ART_RING_STEP(2) ART_RING_STEP(3)
-                ART_RING_STEP(4) ART_RING_STEP(5)
-                ART_RING_STEP(6) ART_RING_STEP(7)
+                ART_RING_STEP(0, 8) ART_RING_STEP(1, 8)
+                ART_RING_STEP(2, 8) ART_RING_STEP(3, 8)
+                ART_RING_STEP(4, 8) ART_RING_STEP(5, 8)
+                ART_RING_STEP(6, 8) ART_RING_STEP(7, 8)
             }
-#undef ART_RING_STEP
         } else {
             for (int r = 0; r < nr; ++r) {           // few samples per point (field-scale prediction): nothing to pipeline
                 float u, e;
@@ -1398,7 +1398,6 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
     if (tid == 0 && pass == win.npass - 1) *s_next = (int)(gridDim.x + next_item);
     __syncthreads();
   }
-       // (diagnostic build: the flush is not stamped apart from the trace here)
     if (tid < (BLOCKING ? 3 : 2) && s_cnt[tid]) atomicAdd(&counts[tid * a.H + h], s_cnt[tid]);
 }
 
@@ -2421,7 +2420,6 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     const bool packed = !CYL && a.pack_edge != 0 && win.npass == 1 && n_pts <= kPackPoints && n_pts <= kPackTrips * (int)blockDim.x &&
                         win.tw >= 2 && win.th >= 2;
     if (packed) pack_edge_points(a, pl, inc, org, nrm, p0, n_pts, win, a.pack_edge, s_edge, perm);
-         // (diagnostic build: end of the edge partition; slot 5 is read out of order by tools/timeline_report.py)
     [[maybe_unused]] const unsigned wm1_bits = f32_bits(pl.wm1), hm1_bits = f32_bits(pl.hm1);
     const float lds_base = (float)(unsigned)(size_t)(lds_f32*)gtile;
     const float e0f = (float)win.e0, tw4f = (float)(4 * win.tw), u0f = (float)win.u0;
@@ -2432,9 +2430,8 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     const bool first = pass == 0;
     if (tid == 0 && pass == win.npass - 1) next_item = fetch_work_item(work_counter, a);
     {   // stage dL/dflux rows (flat row k = output row Hh-1-k) into LDS, un-flipped: stage_grad_window
-        // (until late in round 3 through registers, four rows per wave in flight - the #else branch: 6-8 us per item,
-        //  tools/timeline.sh; eight rows measured 3.65 against 3.53 ms for the kernel, twelve 4.4 - the batch's registers are
-        //  allocated on top of the ray loop's)
+        // (until late in round 3 through registers, four rows per wave in flight: 6-8 us per item, tools/timeline.sh; eight rows
+        //  measured 3.65 against 3.53 ms for the kernel, twelve 4.4 - the batch's registers are allocated on top of the ray loop's)
         const int64_t gbase = (int64_t)(a.Hh - 1 - pu0) * a.W + win.e0;
         stage_grad_window(G + gbase, a.W, win.tw, pth, gtile, wave, lane, nwaves);
     }
@@ -2446,7 +2443,6 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     const unsigned long long win_ok = (win.tw >= 2 && pth >= 2) ? ~0ull : 0ull;
     if (win_ok == 0ull && tid < 2) gtile[tid] = 0.0f;
     __syncthreads();
-    if (first) { }      // (diagnostic build: window + edge partition | staging | trace)
 
     const float pu0f = (float)pu0;
     const unsigned thm2_bits = f32_bits((float)(pth - 2));
@@ -2633,23 +2629,12 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
             const int64_t step = next_r + 1 < nr ? a.sr : 0;
             bu_ += step; be_ += step; ++next_r;
         };
-        if (nr >= 8) {                                // the distortion ring of trace_fwd_item_lean
+        if (nr >= 8) {                                // the distortion ring of trace_fwd_item_lean, two slots deep
             [[maybe_unused]] float su0, se0, su1, se1, su2, se2, su3, se3, su4, se4, su5, se5, su6, se6, su7, se7;
             request(0, su0, se0); request(1, su1, se1);
-#define ART_RING_STEP(j)                                                            \
-            {                                                                       \
-                float u, e;                                                         \
-                asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(u), "=v"(e) : "v"(su##j), "v"(se##j) : "memory"); \
-                request(k + j + 2, su##j, se##j);                      \
-                trace_one(u, e, k + j < nr ? ~0ull : 0ull);                          \
-                /* a ray's arithmetic stays inside its step: hoisting the next step's head above it made the */ \
-                /* compiler spill the ray's live values around the hoisted code */   \
-                __builtin_amdgcn_sched_barrier(0);                                  \
-            }
             for (int k = 0; k < nr; k += 2) {
-                ART_RING_STEP(0) ART_RING_STEP(1)
+                ART_RING_STEP(0, 2) ART_RING_STEP(1, 2)
             }
-#undef ART_RING_STEP
         } else {
             for (int r = 0; r < nr; ++r) {
                 float u, e;
@@ -2718,6 +2703,8 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
         for (int c = tid; c < n_prims * 12; c += blockDim.x) slab[c] = (float)s_tab.grad[c];
     }
 }
+
+#undef ART_RING_STEP
 
 // Persistent workgroups over the work-item queue, like the forward kernel.
 // The lean instantiation is compiled for 1024-thread workgroups (118 registers since the gradient window is staged with LDS-direct
@@ -3326,6 +3313,26 @@ static bool bwd_uses_lean_block(bool blocking, int64_t T, int64_t Tc)
     return blocking && debug_env_int("ARTIST_HIP_LEAN", 1) != 0 && T > 0 && Tc == 0 && debug_env_int("ARTIST_HIP_BLOCK_LEAN", 1) != 0;
 }
 
+// One instantiation of the windowed forward / backward kernel: its dynamic-LDS limit, then the launch.
+template <bool IL, bool CY, bool BL, int LN>
+static int launch_fwd_lds(const FwdLaunch& launch, int64_t blocks, int threads, size_t lds, hipStream_t stream)
+{
+    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_fwd_lds_kernel<IL, CY, BL, LN>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((trace_fwd_lds_kernel<IL, CY, BL, LN>), dim3((unsigned)blocks), dim3(threads), lds, stream, launch);
+    return ART_OK;
+}
+template <bool IL, bool AT, bool CY, bool BL, bool LN>
+static int launch_bwd_lds(const TraceArgs& a, const float* grad_flux, float4* go, float4* gn, float* prim_slabs, unsigned* work_counter,
+                          int64_t blocks, int threads, size_t lds, hipStream_t stream)
+{
+    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_bwd_lds_kernel<IL, AT, CY, BL, LN>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((trace_bwd_lds_kernel<IL, AT, CY, BL, LN>), dim3((unsigned)blocks), dim3(threads), lds, stream, a, grad_flux, go, gn,
+                       prim_slabs, work_counter);
+    return ART_OK;
+}
+
 }  // namespace art
 
 using namespace art;
@@ -3432,18 +3439,8 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
             launch_lean = [=, &side]() -> int {
                 hipStream_t lean_stream = stream;
                 if (ss != nullptr && ss->start()) { side.s = ss; lean_stream = ss->side; }
-                if (il_l) {
-                    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_fwd_lds_kernel<true, false, false, 1>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
-                    hipLaunchKernelGGL((trace_fwd_lds_kernel<true, false, false, 1>), dim3((unsigned)blocks_l), dim3(threads_l),
-                                       lds_l, lean_stream, launch);
-                } else {
-                    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_fwd_lds_kernel<false, false, false, 1>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
-                    hipLaunchKernelGGL((trace_fwd_lds_kernel<false, false, false, 1>), dim3((unsigned)blocks_l), dim3(threads_l),
-                                       lds_l, lean_stream, launch);
-                }
-                return ART_OK;
+                return il_l ? launch_fwd_lds<true, false, false, 1>(launch, blocks_l, threads_l, lds_l, lean_stream)
+                            : launch_fwd_lds<false, false, false, 1>(launch, blocks_l, threads_l, lds_l, lean_stream);
             };
             if (mixed_split) planar_done = true; else a.split = 2;
         }
@@ -3518,11 +3515,9 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
 #define ART_LAUNCH_FWD(IL, CY, BL, LN)                                                                           \
         do {                                                                                                     \
             const int64_t blocks = ((CY && LN == 0) || (BL && LN == 0 && !kBlockingPersistentFwd)) ? items : persistent_blocks;     \
-            ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_fwd_lds_kernel<IL, CY, BL, LN>),    \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
             const FwdLaunch launch = {a, flux, counts, work_counters[CY ? 1 : 0]};                               \
-            hipLaunchKernelGGL((trace_fwd_lds_kernel<IL, CY, BL, LN>), dim3((unsigned)blocks), dim3(CY ? std::min(cfg.block, kCylFwdThreads) : cfg.block),  \
-                               lds, stream, launch);                                                             \
+            const int rc = launch_fwd_lds<IL, CY, BL, LN>(launch, blocks, CY ? std::min(cfg.block, kCylFwdThreads) : cfg.block, lds, stream); \
+            if (rc != ART_OK) return rc;                                                                         \
         } while (0)
 #define ART_LAUNCH_FWD_TYPE(CY)                                                                                  \
         do {                                                                                                     \
@@ -3707,18 +3702,8 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
                 launch_lean = [=, &side]() -> int {
                     hipStream_t lean_stream = stream;
                     if (ss != nullptr && ss->start()) { side.s = ss; lean_stream = ss->side; }
-                    if (il) {
-                        ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_bwd_lds_kernel<true, false, false, false, true>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
-                        hipLaunchKernelGGL((trace_bwd_lds_kernel<true, false, false, false, true>), dim3((unsigned)blocks_l),
-                                           dim3(threads_l), lds_l, lean_stream, al, grad_flux, go, gn, prim_slabs, wc);
-                    } else {
-                        ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_bwd_lds_kernel<false, false, false, false, true>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l));
-                        hipLaunchKernelGGL((trace_bwd_lds_kernel<false, false, false, false, true>), dim3((unsigned)blocks_l),
-                                           dim3(threads_l), lds_l, lean_stream, al, grad_flux, go, gn, prim_slabs, wc);
-                    }
-                    return ART_OK;
+                    return il ? launch_bwd_lds<true, false, false, false, true>(al, grad_flux, go, gn, prim_slabs, wc, blocks_l, threads_l, lds_l, lean_stream)
+                              : launch_bwd_lds<false, false, false, false, true>(al, grad_flux, go, gn, prim_slabs, wc, blocks_l, threads_l, lds_l, lean_stream);
                 };
                 if (mixed_split) planar_done = true; else a.split = 2;
             }
@@ -3737,14 +3722,12 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
 #define ART_LAUNCH_BWD(IL, AT, CY, BL, LN)                                                                       \
         do {                                                                                                     \
             const int64_t blocks = ((CY && !LN && !kCylPersistentBwd) || (!CY && BL && !LN && !kBlockingPersistentBwd)) ? items : persistent_blocks; \
-            ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_bwd_lds_kernel<IL, AT, CY, BL, LN>),\
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
             unsigned* work_counter = stream_work_counters(stream);                                               \
             if (work_counter == nullptr) { g_last_hip_error = (int)hipErrorOutOfMemory; return ART_ELAUNCH; }    \
             work_counter += CY ? 6 : 5;                       /* backward: planar / cylinder launch */          \
-            hipLaunchKernelGGL((trace_bwd_lds_kernel<IL, AT, CY, BL, LN>), dim3((unsigned)blocks),               \
-                               dim3(std::min(cfg.block, CY ? kCylBwdThreads : (BL ? (LN ? kLeanBlockBwdThreads : kBlockingBwdThreads) : 1024))), lds, stream, a, grad_flux, \
-                               go, gn, prim_slabs, work_counter);                                                \
+            const int threads = std::min(cfg.block, CY ? kCylBwdThreads : (BL ? (LN ? kLeanBlockBwdThreads : kBlockingBwdThreads) : 1024)); \
+            const int rc = launch_bwd_lds<IL, AT, CY, BL, LN>(a, grad_flux, go, gn, prim_slabs, work_counter, blocks, threads, lds, stream); \
+            if (rc != ART_OK) return rc;                                                                         \
         } while (0)
 #define ART_LAUNCH_BWD_BL(CY, BL, LN)                                                                            \
         do {                                                                                                     \
