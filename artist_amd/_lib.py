@@ -109,6 +109,17 @@ _BY_HEADER = {
 SIGNATURES = {name: signature for table in _BY_HEADER.values() for name, signature in table.items()}
 HEADERS = {header: tuple(table) for header, table in _BY_HEADER.items()}
 
+# Entry points added since the lists above were pinned, by their header under include/extensions/: same form, bound by bind()
+# and called through call() like the rest, each header compared with its declarations by a test of its own.
+_BY_EXTENSION_HEADER = {
+    "extensions/artist_hip_sunshape.h": {
+        "art_sample_radial_distortions": (_c_int, [_c_i64, _ptr, _c_i64, _c_i64, _c_i64, _c_flt, _c_flt, _ptr, _c_i64, _ptr, _ptr]),
+    },
+}
+
+EXTENSION_SIGNATURES = {name: signature for table in _BY_EXTENSION_HEADER.values() for name, signature in table.items()}
+EXTENSION_HEADERS = {header: tuple(table) for header, table in _BY_EXTENSION_HEADER.items()}
+
 _LIB = None
 
 
@@ -124,9 +135,9 @@ def build(verbose: bool = False) -> pathlib.Path:
 
 
 def bind(handle: ctypes.CDLL, path) -> ctypes.CDLL:
-    """Give every entry point of ``SIGNATURES`` its types on ``handle`` (a build of the library loaded from ``path``) and
+    """Give every entry point of ``SIGNATURES`` and ``EXTENSION_SIGNATURES`` its types on ``handle`` (a build of the library loaded from ``path``) and
     check the ABI version."""
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **EXTENSION_SIGNATURES}.items():
         try:
             fn = getattr(handle, name)
         except AttributeError as exc:

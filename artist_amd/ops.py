@@ -179,13 +179,8 @@ def reflect_directions(incident: torch.Tensor, normals: torch.Tensor) -> torch.T
     return out
 
 
-def sample_distortions(rows, number_of_rays: int, number_of_points: int, seed: int, loc, scale_tril, device) -> torch.Tensor:
-    """Rows ``rows`` of the Gaussian sun-shape sample, ``[len(rows), R, P, 2]`` fp32 with ``(u, e)`` interleaved, drawn in one
-    launch on the current stream of ``device`` (``art_sample_distortions``, include/artist_hip_sampler.h).  Row ``rows[k]``
-    comes from a Philox stream keyed by ``(seed, rows[k])``: the same bits whatever the other rows of the call.
-
-    ``loc`` (2 values) and ``scale_tril`` (2x2, lower triangular) are HOST values: the call reads nothing back from the device.
-    ``rows`` is a list of ints or an integer tensor (a list travels through pinned memory, without a synchronisation)."""
+def _sampler_call(rows, number_of_rays: int, number_of_points: int, seed: int, device):
+    """What both samplers do before their launch: ``(device, seed as int64, rows on the device, n, R, P, out)``."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.ArtistHipError(
@@ -202,12 +197,43 @@ def sample_distortions(rows, number_of_rays: int, number_of_points: int, seed: i
             rows.to(torch.int64).contiguous().pin_memory().to(dev, non_blocking=True)
     else:
         rows_t = torch.tensor([int(r) for r in rows], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-    (lu, le), ((l00, _), (l10, l11)) = [float(v) for v in loc], [[float(v) for v in r] for r in scale_tril]
     n = int(rows_t.shape[0])
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed as a 64-bit two's-complement value
     seed = seed - (1 << 64) if seed >= (1 << 63) else seed
     out = torch.empty((n, R, P, 2), dtype=torch.float32, device=dev)
-    _timed_call("art_sample_distortions", dev, int(seed), rows_t.data_ptr(), n, R, P, lu, le, l00, l10, l11, out.data_ptr())
+    return dev, int(seed), rows_t, n, R, P, out
+
+
+def sample_distortions(rows, number_of_rays: int, number_of_points: int, seed: int, loc, scale_tril, device) -> torch.Tensor:
+    """Rows ``rows`` of the Gaussian sun-shape sample, ``[len(rows), R, P, 2]`` fp32 with ``(u, e)`` interleaved, drawn in one
+    launch on the current stream of ``device`` (``art_sample_distortions``, include/artist_hip_sampler.h).  Row ``rows[k]``
+    comes from a Philox stream keyed by ``(seed, rows[k])``: the same bits whatever the other rows of the call.
+
+    ``loc`` (2 values) and ``scale_tril`` (2x2, lower triangular) are HOST values: the call reads nothing back from the device.
+    ``rows`` is a list of ints or an integer tensor (a list travels through pinned memory, without a synchronisation)."""
+    dev, seed, rows_t, n, R, P, out = _sampler_call(rows, number_of_rays, number_of_points, seed, device)
+    (lu, le), ((l00, _), (l10, l11)) = [float(v) for v in loc], [[float(v) for v in r] for r in scale_tril]
+    _timed_call("art_sample_distortions", dev, seed, rows_t.data_ptr(), n, R, P, lu, le, l00, l10, l11, out.data_ptr())
+    return out
+
+
+def sample_radial_distortions(rows, number_of_rays: int, number_of_points: int, seed: int, loc, table, device) -> torch.Tensor:
+    """``sample_distortions`` for a radially symmetric sun shape (``art_sample_radial_distortions``,
+    include/extensions/artist_hip_sunshape.h): same rows, layout and
+    streams, the radius of a ray drawn from ``table``, the fp32 ``[K+1]`` quantile table of squared radii that
+    ``artist_amd.scene.radial_quantile_table`` builds, ``1 <= K <= 4096``.
+
+    ``loc`` (2 values) is a HOST value; ``table`` is a tensor on ``device`` and stays there: nothing is read back."""
+    dev, seed, rows_t, n, R, P, out = _sampler_call(rows, number_of_rays, number_of_points, seed, device)
+    if not isinstance(table, torch.Tensor) or table.dim() != 1 or table.dtype != torch.float32 or table.device != dev \
+            or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous 1-D float32 tensor on {dev}")
+    K = int(table.shape[0]) - 1
+    if not 1 <= K <= 4096:
+        raise ValueError(f"table must hold K+1 nodes with 1 <= K <= 4096, got {K + 1} values")
+    lu, le = (float(v) for v in loc)
+    _timed_call("art_sample_radial_distortions", dev, seed, rows_t.data_ptr(), n, R, P, lu, le, table.data_ptr(), K,
+                out.data_ptr())
     return out
 
 

@@ -146,9 +146,12 @@ def read_light_source(config, name=None) -> dict:
     if kind != "sun":
         raise KeyError(f"Currently the selected light source: {kind} is not supported.")
     params = dict(distribution_type=_text(config["distribution_parameters"]["distribution_type"]))
-    for key in ("mean", "covariance"):
+    for key in ("mean", "covariance", "half_angle", "circumsolar_ratio"):
         if key in config["distribution_parameters"].keys():
             params[key] = float(config["distribution_parameters"][key][()])
+    for key in ("profile_angles", "profile_radiance"):                 # a "tabulated" sun (artist_amd.scene.Sun)
+        if key in config["distribution_parameters"].keys():
+            params[key] = np.asarray(config["distribution_parameters"][key][()], dtype=np.float64)
     return dict(name=name, number_of_rays=int(config["number_of_rays"][()]), distribution_parameters=params)
 
 

@@ -13,19 +13,164 @@ Reference attribute sources: ``artist/field/heliostat_group.py:133-222, 225-315`
 """
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nurbs_control_points
 
 
 #: Distortion samplers of :class:`Sun` on the device: ``"torch"`` (the default: one seeded ``torch.randn`` per heliostat row)
-#: and ``"hip"`` (``art_sample_distortions``: one launch, a Philox stream per (seed, row), with a per-sun sample cache).
+#: and ``"hip"`` (``art_sample_distortions`` / ``art_sample_radial_distortions``: one launch, a Philox stream per (seed, row),
+#: with a per-sun sample cache).
 SAMPLERS = ("torch", "hip")
+
+#: ``distribution_type`` values of :class:`Sun` next to ``"normal"``: radially symmetric shapes, each held as a quantile table.
+RADIAL_TYPES = ("pillbox", "buie", "tabulated")
+SOLAR_DISC_HALF_ANGLE = 4.65e-3         # rad: the edge of the solar disc
+BUIE_EXTENT = 43.6e-3                   # rad: where Buie's circumsolar profile ends
+RADIAL_TABLE_INTERVALS = 1024           # K of the "buie" and "tabulated" tables (a pillbox is exact with K = 1)
+
+
+def buie_profile(circumsolar_ratio: float):
+    """Buie, Monger and Dey (2003): radiance ``B(theta)``, ``theta`` in rad (numpy in, numpy out).  With theta in mrad,
+    ``B = cos(0.326 theta) / cos(0.308 theta)`` on the disc (``theta <= 4.65``), ``exp(kappa) theta^gamma`` in the aureole
+    (``4.65 < theta <= 43.6``) and 0 beyond, ``kappa = 0.9 ln(13.5 chi) chi^-0.3``, ``gamma = 2.2 ln(0.52 chi) chi^0.43 - 0.1``.
+
+    ``chi`` goes into the formulas as it is: the share of the energy that they put outside the disc differs slightly from
+    ``chi`` (0.0431 for chi = 0.05, 0.274 for chi = 0.3), and no correction of it is applied.  The two
+    branches do not meet at 4.65 mrad."""
+    chi = float(circumsolar_ratio)
+    kappa = 0.9 * math.log(13.5 * chi) * chi ** -0.3
+    gamma = 2.2 * math.log(0.52 * chi) * chi ** 0.43 - 0.1
+
+    def radiance(theta):
+        mrad = np.asarray(theta, dtype=np.float64) * 1e3
+        disc = np.cos(0.326 * mrad) / np.cos(0.308 * mrad)
+        aureole = math.exp(kappa) * np.maximum(mrad, 1.0) ** gamma             # (only read beyond the disc)
+        return np.where(mrad <= SOLAR_DISC_HALF_ANGLE * 1e3, disc, np.where(mrad <= BUIE_EXTENT * 1e3, aureole, 0.0))
+
+    return radiance
+
+
+def radial_quantile_table(profile, K: int, theta_max: float | None = None, breaks=()) -> torch.Tensor:
+    """The quantile table of a radially symmetric sun shape: ``t2[0..K]``, fp32 and non-decreasing, ``t2[k]`` the squared
+    angular radius (rad^2) below which the fraction ``k/K`` of the energy lies.  A ray at angular distance ``theta`` from the
+    sun's centre has density proportional to ``B(theta) sin(theta)``; the samplers interpolate ``theta^2`` linearly in the
+    quantile between two nodes, which is K annuli of equal energy with constant radiance inside each.
+
+    ``profile`` is a callable ``B(theta)`` (a float64 numpy array of angles in rad in, radiances out) on ``[0, theta_max]``,
+    with ``breaks`` the angles at which it jumps, or a sampled profile ``(angles, radiance)``: piecewise linear between the
+    angles, zero outside them.
+
+    Integration (trapezoid) and inversion run in float64 numpy on a grid of at least 32 K points per smooth piece, so a node's
+    radius is far closer than one annulus.  At a jump the grid has a point on either side (the angle and the next float64
+    above it), so that neither branch leaks into the other."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"K must be >= 1, got {K}")
+    if callable(profile):
+        if theta_max is None or not theta_max > 0:
+            raise ValueError("theta_max must be > 0 for a callable profile")
+        edges = [0.0] + sorted(float(b) for b in breaks if 0.0 < float(b) < float(theta_max)) + [float(theta_max)]
+        per_piece = max(32 * K, 1 << 15)
+        pieces = []
+        for lo, hi in zip(edges[:-1], edges[1:]):
+            piece = np.linspace(lo, hi, per_piece + 1)
+            if lo > 0.0:
+                piece[0] = np.nextafter(lo, np.inf)                  # the far side of the jump at `lo`
+            pieces.append(piece)
+        grid = np.concatenate(pieces)
+        radiance = np.asarray(profile(grid), dtype=np.float64)
+    else:
+        angles, values = (np.asarray(a, dtype=np.float64) for a in profile)
+        per_piece = max(2, -(-32 * K // (len(angles) - 1)))
+        steps = np.arange(per_piece) / per_piece
+        grid = np.append((angles[:-1, None] + steps[None, :] * np.diff(angles)[:, None]).reshape(-1), angles[-1])
+        radiance = np.interp(grid, angles, values)
+    if radiance.shape != grid.shape or not np.isfinite(radiance).all() or (radiance < 0).any():
+        raise ValueError("the radiance profile must be finite and >= 0")
+    weight = radiance * np.sin(grid)
+    energy = np.concatenate(([0.0], np.cumsum(0.5 * (weight[1:] + weight[:-1]) * np.diff(grid))))
+    if not energy[-1] > 0:
+        raise ValueError("the radiance profile must have a positive integral")
+    target = np.arange(K + 1) / K * energy[-1]
+    hi = np.clip(np.searchsorted(energy, target, side="left"), 1, len(grid) - 1)
+    hi[0] = min(int(np.searchsorted(energy, 0.0, side="right")), len(grid) - 1)   # no energy below the first node
+    lo = hi - 1
+    span = energy[hi] - energy[lo]
+    frac = np.where(span > 0, (target - energy[lo]) / np.where(span > 0, span, 1.0), 0.0)
+    g2 = grid * grid
+    t2 = np.maximum.accumulate(g2[lo] + frac * (g2[hi] - g2[lo]))
+    return torch.from_numpy(t2.astype(np.float32))
+
+
+class RadialSunShape:
+    """What ``Sun.distribution`` is for a radial shape: ``loc`` (2 values, the sun's centre in (u, e)), ``quantile_table``
+    (:func:`radial_quantile_table`, on the device of ``loc``) and ``sample(shape)``, the table rule in torch ops: a uniform
+    quantile picks ``theta^2`` from the table, a uniform azimuth turns ``theta`` into ``(u, e) = loc + theta (cos, sin)``."""
+
+    def __init__(self, loc: torch.Tensor, quantile_table: torch.Tensor) -> None:
+        self.loc = loc
+        self.quantile_table = quantile_table
+
+    def sample(self, sample_shape=()) -> torch.Tensor:
+        """``[*sample_shape, 2]`` draws from torch's current generator of the device of ``loc``."""
+        return self.transform_(torch.rand(tuple(sample_shape) + (2,), dtype=self.loc.dtype, device=self.loc.device))
+
+    def transform_(self, uniform: torch.Tensor) -> torch.Tensor:
+        """Turn ``uniform[..., 0:2]`` = (quantile, azimuth in revolutions) into ``(u, e)`` in place."""
+        t2 = self.quantile_table
+        K = t2.shape[0] - 1
+        t = uniform[..., 0] * K
+        i = t.long().clamp_(max=K - 1)
+        lo = t2[i]
+        theta = torch.sqrt(lo + (t - i) * (t2[i + 1] - lo))
+        phi = uniform[..., 1] * (2.0 * math.pi)
+        uniform[..., 0] = self.loc[0] + theta * torch.cos(phi)
+        uniform[..., 1] = self.loc[1] + theta * torch.sin(phi)
+        return uniform
+
+
+def _radial_table(params: dict) -> torch.Tensor:
+    """The quantile table of a radial ``distribution_type``, its parameters checked (``ValueError`` names the parameter)."""
+    kind = params["distribution_type"]
+    if kind == "pillbox":
+        half_angle = float(params["half_angle"])
+        if not (half_angle > 0 and math.isfinite(half_angle)):
+            raise ValueError(f"half_angle must be > 0, got {half_angle}")
+        return torch.tensor([0.0, half_angle * half_angle], dtype=torch.float64).float()
+    if kind == "buie":
+        chi = float(params["circumsolar_ratio"])
+        if not 0.0 < chi < 1.0:
+            raise ValueError(f"circumsolar_ratio must lie in (0, 1), got {chi}")
+        return radial_quantile_table(buie_profile(chi), RADIAL_TABLE_INTERVALS, theta_max=BUIE_EXTENT,
+                                     breaks=(SOLAR_DISC_HALF_ANGLE,))
+    for name in ("profile_angles", "profile_radiance"):
+        if params.get(name) is None:
+            raise ValueError(f"a tabulated sun needs {name}")
+    angles = np.asarray(torch.as_tensor(params["profile_angles"]).detach().cpu().numpy(), dtype=np.float64)
+    radiance = np.asarray(torch.as_tensor(params["profile_radiance"]).detach().cpu().numpy(), dtype=np.float64)
+    if angles.ndim != 1 or angles.size < 2 or not np.isfinite(angles).all() or angles[0] < 0 or (np.diff(angles) <= 0).any():
+        raise ValueError("profile_angles must be at least two strictly increasing angles, the first >= 0")
+    if radiance.shape != angles.shape or not np.isfinite(radiance).all() or (radiance < 0).any():
+        raise ValueError(f"profile_radiance must be {angles.size} values >= 0, one per angle of profile_angles")
+    if not (radiance > 0).any():
+        raise ValueError("profile_radiance must have a positive integral")
+    return radial_quantile_table((angles, radiance), RADIAL_TABLE_INTERVALS)
 
 
 class Sun:
-    """Gaussian sun shape; ``get_distortions`` = seeded ``MultivariateNormal`` sample permuted to
-    ``(u, e)`` views of one interleaved buffer (artist/scene/sun.py:96-119, 199-234).
+    """A sun shape and its sample.  ``distribution_type`` ``"normal"`` (the default, the reference's only one) is the Gaussian;
+    ``get_distortions`` = seeded ``MultivariateNormal`` sample permuted to ``(u, e)`` views of one interleaved buffer
+    (artist/scene/sun.py:96-119, 199-234).
+
+    The radially symmetric types (``RADIAL_TYPES``) are an extension: ``"pillbox"`` (``half_angle``, default
+    4.65e-3 rad), ``"buie"`` (``circumsolar_ratio``, default 0.05: :func:`buie_profile`, chi uncorrected) and ``"tabulated"``
+    (``profile_angles`` in rad and ``profile_radiance``: piecewise linear, zero outside).  Each is built once into a quantile
+    table (``quantile_table``, on ``device``), ``distribution`` is then a :class:`RadialSunShape` centred on ``mean``, and a
+    ray's ``(u, e)`` is ``loc + theta (cos phi, sin phi)``: the small-angle reading the Gaussian makes too.
 
     ``sampler`` chooses how a GPU-resident sun draws (``SAMPLERS``); it may be set on a light source that is already
     loaded.  With ``"hip"`` the last sample is kept (one per sun) and handed out again, without a launch or a
@@ -36,15 +181,23 @@ class Sun:
                  device: torch.device | None = None, sampler: str = "torch") -> None:
         params = dict(distribution_type="normal", mean=0.0, covariance=4.3681e-06)
         params.update(distribution_parameters or {})
-        if params["distribution_type"] != "normal":
+        kind = params["distribution_type"]
+        if kind != "normal" and kind not in RADIAL_TYPES:
             raise ValueError("Unknown sunlight distribution type.")
+        if kind == "pillbox":
+            params.setdefault("half_angle", SOLAR_DISC_HALF_ANGLE)
+        elif kind == "buie":
+            params.setdefault("circumsolar_ratio", 0.05)
         self.distribution_parameters = params
         self.number_of_rays = number_of_rays
         mean = torch.tensor([params["mean"], params["mean"]], dtype=torch.float, device=device)
-        cov = torch.tensor([[params["covariance"], 0], [0, params["covariance"]]], dtype=torch.float, device=device)
-        self.distribution = torch.distributions.MultivariateNormal(mean, cov)
+        if kind == "normal":
+            cov = torch.tensor([[params["covariance"], 0], [0, params["covariance"]]], dtype=torch.float, device=device)
+            self.distribution = torch.distributions.MultivariateNormal(mean, cov)
+        else:
+            self.distribution = RadialSunShape(mean, _radial_table(params).to(mean.device))
         self._law = None            # (distribution, tensor versions, host law) - see _host_law
-        self._cache = None          # (key, buffer, buffer version) of the last "hip" draw
+        self._cache = None          # (key, buffer, buffer version, table, table version) of the last "hip" draw
         self._sampler = None
         self.sampler = sampler
 
@@ -59,6 +212,18 @@ class Sun:
         if name != self._sampler:
             self._sampler = name
             self._cache = None
+
+    @property
+    def quantile_table(self) -> torch.Tensor | None:
+        """The quantile table of a radial sun (fp32 ``[K+1]`` on the sun's device; None for a normal sun).  It may be
+        replaced or written in place: the ``"hip"`` sampler notices either and draws anew."""
+        return getattr(self.distribution, "quantile_table", None)
+
+    @quantile_table.setter
+    def quantile_table(self, table: torch.Tensor) -> None:
+        if not isinstance(self.distribution, RadialSunShape):
+            raise ValueError("only a radial sun has a quantile table")
+        self.distribution.quantile_table = table
 
     def clear_distortion_cache(self) -> None:
         """Drop the kept ``"hip"`` sample (its memory is freed once no caller holds a view of it)."""
@@ -95,19 +260,27 @@ class Sun:
         (``loc + scale_tril @ eps``), written element-wise: the batched 2x2 matrix-vector product of torch's
         ``MultivariateNormal.sample`` faulted on ROCm for ~1e7 and more samples.
 
-        ``sampler == "torch"``: a seeded ``torch.randn`` per row; ``"hip"``: ``art_sample_distortions`` (Philox4x32-10
-        keyed by (seed, row)), cached per sun (class docstring), and no CPU fallback."""
+        ``sampler == "torch"``: a seeded ``torch.randn`` per row (``torch.rand`` and the table rule for a radial sun);
+        ``"hip"``: ``art_sample_distortions`` / ``art_sample_radial_distortions`` (Philox4x32-10 keyed by (seed, row),
+        DESIGN.md 4.5), cached per sun (class docstring), and no CPU fallback."""
         if self._sampler == "hip":
             return self._hip_rows(rows, number_of_points, random_seed)
-        loc, tril = self.distribution.loc, self.distribution.scale_tril
+        dist = self.distribution
+        loc = dist.loc
         if loc.device.type == "cpu":
             return None
+        radial = isinstance(dist, RadialSunShape)
+        draw = torch.rand if radial else torch.randn
         rows = [int(r) for r in rows]
         out = torch.empty((len(rows), self.number_of_rays, number_of_points, 2), dtype=loc.dtype, device=loc.device)
         gen = torch.Generator(device=loc.device)
         for k, row in enumerate(rows):
             gen.manual_seed((int(random_seed) * 1000003 + row) & 0x7FFFFFFFFFFFFFFF)
-            torch.randn(out[k].shape, generator=gen, dtype=loc.dtype, device=loc.device, out=out[k])
+            draw(out[k].shape, generator=gen, dtype=loc.dtype, device=loc.device, out=out[k])
+        if radial:
+            distortions_u, distortions_e = dist.transform_(out).permute(3, 0, 1, 2)
+            return distortions_u, distortions_e
+        tril = dist.scale_tril
         if float(tril[1, 0]) != 0.0:
             out[..., 1] = tril[1, 0] * out[..., 0] + tril[1, 1] * out[..., 1]
         else:
@@ -119,14 +292,22 @@ class Sun:
         return distortions_u, distortions_e
 
     def _host_law(self):
-        """``(loc, scale_tril)`` of the current distribution as host floats.  Read from the device (one synchronisation)
-        only when ``distribution`` is a new object or one of its two tensors was written since the last read."""
+        """``(loc, scale_tril)`` of the current distribution as host floats (``(loc, None)`` for a radial sun, whose table stays
+        on the device).  Read from the device (one synchronisation) only when ``distribution`` is a new object or one of its
+        tensors was written since the last read."""
         dist = self.distribution
-        loc, tril = dist.loc, dist.scale_tril
-        versions = (loc._version, tril._version)
+        radial = isinstance(dist, RadialSunShape)
+        loc, tril = dist.loc, None if radial else dist.scale_tril
+        versions = (loc._version, None if radial else tril._version)
         kept = self._law
         if kept is not None and kept[0] is dist and kept[1] == versions:
             return kept[2]
+        if radial:
+            if tuple(loc.shape) != (2,):
+                raise ValueError(f"the centre of a radial sun must be 2 values, got loc {tuple(loc.shape)}")
+            law = (tuple(loc.detach().float().cpu().tolist()), None)
+            self._law = (dist, versions, law)
+            return law
         if tuple(loc.shape) != (2,) or tuple(tril.shape) != (2, 2):
             raise ValueError(f"the sun's distribution must be a single 2-D normal, got loc {tuple(loc.shape)}, "
                              f"scale_tril {tuple(tril.shape)}")
@@ -143,14 +324,19 @@ class Sun:
                                       "there is no CPU fallback")
         rows = tuple(int(r) for r in rows)
         law = self._host_law()
+        table = self.quantile_table     # a radial sun's law: the same tensor, unwritten since the draw (None: a normal sun)
         key = (int(random_seed), rows, int(self.number_of_rays), int(number_of_points), loc.device, law)
         kept = self._cache
-        if kept is not None and kept[0] == key and kept[1]._version == kept[2]:
+        if kept is not None and kept[0] == key and kept[1]._version == kept[2] and kept[3] is table and \
+                (table is None or kept[4] == table._version):
             buf = kept[1]
         else:
             self._cache = None          # the old sample goes first: at most one per sun is alive while the new one is drawn
-            buf = ops.sample_distortions(rows, key[2], key[3], key[0], law[0], law[1], loc.device)
-            self._cache = (key, buf, buf._version)
+            if table is None:
+                buf = ops.sample_distortions(rows, key[2], key[3], key[0], law[0], law[1], loc.device)
+            else:
+                buf = ops.sample_radial_distortions(rows, key[2], key[3], key[0], law[0], table, loc.device)
+            self._cache = (key, buf, buf._version, table, None if table is None else table._version)
         distortions_u, distortions_e = buf.permute(3, 0, 1, 2)
         return distortions_u, distortions_e
 

@@ -2,7 +2,9 @@
  * artist_hip_sampler.h - the sun-shape distortion sampler of libartist_hip.so (same library, same conventions and
  * return codes as include/artist_hip.h: device pointers, `stream` is a hipStream_t passed as void*, asynchronous).
  *
- * Kept in a header of its own so that the entry-point list and ABI version of artist_hip.h stay as they are.
+ * Kept in a header of its own so that the entry-point list and ABI version of artist_hip.h stay as they are.  For the
+ * same reason the sampler of the radially symmetric sun shapes (pillbox, Buie, tabulated: art_sample_radial_distortions) is
+ * declared in extensions/artist_hip_sunshape.h, and this header's list stays as it is.
  */
 #ifndef ARTIST_HIP_SAMPLER_H
 #define ARTIST_HIP_SAMPLER_H

@@ -10,8 +10,12 @@
     the tracer rebuilt every step: with a sample drawn once before the loop, with the torch sampler, with the HIP sampler
     without the cache and with it; and, for scale, one tracer reused by every step.
 
+  * --shape pillbox | buie: instead of the above, the radial kernel (art_sample_radial_distortions, the shape's quantile
+    table) next to the Gaussian kernel at the same two sizes, both from device events, alternating in one process
+    -> profiles/sunshape_bench.json.
+
 usage: python tools/sampler_bench.py [--heliostats 1000 --rays 100 --n-eval 50 --steps 10 --warmup 3 --epoch-steps 30]
-                                     [--no-epoch] [--out FILE]
+                                     [--no-epoch] [--shape normal|pillbox|buie] [--out FILE]
 """
 import argparse
 import json
@@ -80,8 +84,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--epoch-steps", type=int, default=30)
     ap.add_argument("--no-epoch", action="store_true", help="draws only (the profiler run)")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "sampler_bench.json"))
+    ap.add_argument("--shape", choices=("normal", "pillbox", "buie"), default="normal",
+                    help="a radial shape: time its kernel against the Gaussian kernel, draws only")
+    ap.add_argument("--out", default=None, help="default: profiles/sampler_bench.json (sunshape_bench.json with --shape)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("sampler_bench.json" if args.shape == "normal" else "sunshape_bench.json"))
     if not torch.cuda.is_available():
         raise SystemExit("sampler_bench needs a GPU")
     from artist_amd import HeliostatRayTracer, _lib, ops
@@ -105,7 +113,11 @@ def main():
 
     sun = Sun(R, device=dev)
     law = sun._host_law()
-    for label, rows in (("field", list(range(H))), ("rank_share", list(range(0, H, max(1, H // args.share)))[:args.share])):
+    sizes = (("field", list(range(H))), ("rank_share", list(range(0, H, max(1, H // args.share)))[:args.share]))
+    if args.shape != "normal":
+        return finish(shape_pair(res, args, ops, Sun(R, dict(distribution_type=args.shape), device=dev), law, sizes, R, P, dev),
+                      args.out)
+    for label, rows in sizes:
         nbytes = len(rows) * R * P * 8
         hip = event_ms(lambda: ops.sample_distortions(rows, R, P, 7, *law, dev), args.steps, args.warmup)
         sun.sampler = "torch"
@@ -195,6 +207,34 @@ def main():
     res["reference_epoch"] = epochs
     print("[sampler] epoch ms: " + ", ".join(f"{k} {v}" for k, v in epochs.items() if k != "what"), flush=True)
     return finish(res, args.out)
+
+
+def shape_pair(res, args, ops, shape_sun, law, sizes, R, P, dev):
+    """The radial kernel and the Gaussian kernel, two rounds each in turn (the same-run spread), per size."""
+    table = shape_sun.quantile_table
+    res["shape"] = {"distribution_type": args.shape, "K": int(table.shape[0]) - 1, "lds_bytes_per_workgroup": 8 * (int(table.shape[0]) - 1)}
+    for label, rows in sizes:
+        nbytes = len(rows) * R * P * 8
+        rows_t = torch.tensor(rows, dtype=torch.int64, device=dev)
+        kernels = {"gaussian": lambda: ops.sample_distortions(rows_t, R, P, 7, *law, dev),
+                   "radial": lambda: ops.sample_radial_distortions(rows_t, R, P, 7, (0.0, 0.0), table, dev)}
+        rounds = {name: [] for name in kernels}
+        for _ in range(2):
+            for name, fn in kernels.items():
+                rounds[name].append(event_ms(fn, args.steps, args.warmup))
+                torch.cuda.empty_cache()
+        entry = {"rows": len(rows), "bytes": nbytes, "write_floor_ms": nbytes / WRITE_RATE * 1e3}
+        for name, got in rounds.items():
+            median = min(r["median_ms"] for r in got)
+            entry[name] = {"rounds": got, "median_ms": median, "GBps": nbytes / median / 1e6,
+                           "fraction_of_write_rate": nbytes / (median * 1e-3) / WRITE_RATE}
+        entry["radial_over_gaussian"] = entry["radial"]["median_ms"] / entry["gaussian"]["median_ms"]
+        res["draws"][label] = entry
+        print(f"[sampler] {label}: {len(rows)} rows, gaussian {entry['gaussian']['median_ms']:.3f} ms, {args.shape} "
+              f"{entry['radial']['median_ms']:.3f} ms (ratio {entry['radial_over_gaussian']:.3f})", flush=True)
+    res["what"] = ("ms per draw from device events; per kernel two rounds of --steps draws, alternating gaussian / radial, "
+                   "median_ms = the lower of the two round medians; rows travel as a device tensor in both")
+    return res
 
 
 def finish(res, out):
