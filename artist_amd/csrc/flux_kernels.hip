@@ -269,7 +269,8 @@ __device__ __forceinline__ void tap_range(float scale, float centre, int n, int 
 // first output index and the (at most four) weights of a column are shared by the 16 pixels of that column and those
 // of a row by its 64 pixels - they are computed once per tile into LDS - and the sum factorises into a horizontal
 // pass (4 global loads per output row and column, kept in LDS) and a vertical pass (4 LDS reads per pixel).  A bitmap
-// whose crop scale needs more than four taps per axis (scale < ~0.6) takes the per-pixel form.
+// whose crop scale needs more than four taps per axis (scale below 0.5: tap_range's interval is 2.008 / scale output indices
+// long, a fifth candidate fits from 4 on) takes the per-pixel form.
 constexpr int kTileX = 64, kTileY = 32, kTaps = 4, kTileRows = 64, kRowUnroll = 4;
 // LOSS = true: the fused crop + PixelLoss adjoint.  grad_out is then the RESIDUAL crop - truth that the forward pass kept, gcom
 // the gradient of the two centre coordinates per unit of 2 gl / sum(truth), and the whole pixel is scaled by that factor at
@@ -951,12 +952,19 @@ static bool crop_args_ok(const void* a, const void* b, const void* c, const void
     return a && b && c && d && B >= 0 && Hh >= 1 && W >= 1 && Hh <= 65535 && Hh * W <= (int64_t)1 << 30 && B <= 65535;
 }
 
+// An empty batch (a rank without an active heliostat) has nothing to launch and nothing to point at: the tensors of such a call
+// are empty, and an empty tensor's data pointer is null.  ART_OK before the pointers are looked at.
+static bool empty_batch(int64_t B, int64_t Hh, int64_t W)
+{
+    return B == 0 && Hh >= 1 && W >= 1;
+}
+
 extern "C" int art_flux_crop_fwd(const float* flux, const float* target_dims, int64_t B, int64_t Hh, int64_t W,
                                  double crop_width, double crop_height, float* out, float* centers, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, out, centers, B, Hh, W)) return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_com_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, centers);
     hipLaunchKernelGGL(flux_crop_fwd_kernel,
                        dim3((unsigned)((W + kFluxBlock - 1) / kFluxBlock), (unsigned)((Hh + kCropRows - 1) / kCropRows), (unsigned)B),
@@ -971,8 +979,8 @@ extern "C" int art_flux_crop_bwd(const float* flux, const float* target_dims, co
                                  float* grad_flux, float* workspace, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, centers, grad_out, B, Hh, W) || !grad_flux || !workspace) return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_crop_bwd_com_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, target_dims, centers,
                        grad_out, (int)Hh, (int)W, (float)crop_width, (float)crop_height, workspace);
     hipLaunchKernelGGL(flux_crop_bwd_tiled_kernel<false>,
@@ -987,10 +995,10 @@ extern "C" int art_flux_loss(const float* prediction, const float* ground_truth,
                              float* loss, const float* grad_loss, float* grad_prediction, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, npix, 1) && (kind == 0 || kind == 1)) return ART_OK;
     if (!prediction || !ground_truth || B < 0 || npix < 1 || (kind != 0 && kind != 1) || (!loss && !grad_prediction) ||
         (grad_prediction && !grad_loss))
         return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_loss_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, prediction, ground_truth, npix,
                        kind, loss, grad_loss, grad_prediction);
     ART_HIP(hipGetLastError());
@@ -1003,9 +1011,9 @@ extern "C" int art_flux_crop_pixel_loss_fwd(const float* flux, const float* targ
                                             void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, ground_truth, loss, B, Hh, W) || !centers4 || (residual != nullptr) != (center_grad_unit != nullptr))
         return ART_EINVAL;
-    if (B == 0) return ART_OK;
     const int P = loss_workgroups_per_bitmap(B, Hh);
     PartScratch* ws = P > 1 ? flux_parts_scratch(stream) : nullptr;
     // LDS for the rows a part samples (a crop never magnifies by much: the rows of a part + 3 cover every scale up to 1), two
@@ -1041,10 +1049,10 @@ extern "C" int art_flux_crop_pixel_loss_bwd(const float* target_dims, const floa
                                             int64_t Hh, int64_t W, double crop_width, double crop_height, float* grad_flux, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(residual, target_dims, center_grad_unit, centers4, B, Hh, W) || !grad_loss || !grad_flux ||
         (grad_loss_stride != 0 && grad_loss_stride != 1))
         return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_crop_bwd_tiled_kernel<true>,
                        dim3((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((Hh + kTileY - 1) / kTileY), (unsigned)B),
                        dim3(256), 0, stream, target_dims, centers4, center_grad_unit, residual, (int)Hh, (int)W, (float)crop_width,
@@ -1056,8 +1064,8 @@ extern "C" int art_flux_crop_pixel_loss_bwd(const float* target_dims, const floa
 extern "C" int art_flux_center_of_mass(const float* flux, int64_t B, int64_t Hh, int64_t W, float* com, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, com, flux, com, B, Hh, W)) return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_com_px_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, com);
     ART_HIP(hipGetLastError());
     return ART_OK;
@@ -1067,8 +1075,8 @@ extern "C" int art_flux_center_of_mass_bwd(const float* com, const float* grad_c
                                            float* grad_flux, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(com, grad_com, grad_flux, com, B, Hh, W)) return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_com_px_bwd_kernel, dim3((unsigned)((Hh * W + kFluxBlock - 1) / kFluxBlock), (unsigned)B), dim3(kFluxBlock),
                        0, stream, com, grad_com, (int)Hh, (int)W, grad_flux);
     ART_HIP(hipGetLastError());
@@ -1080,8 +1088,8 @@ extern "C" int art_flux_crop_kl_loss_fwd(const float* flux, const float* target_
                                          float* record8, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, ground_truth, loss, B, Hh, W) || !record8) return ART_EINVAL;
-    if (B == 0) return ART_OK;
     hipLaunchKernelGGL(flux_crop_kl_loss_fwd_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, target_dims,
                        ground_truth, (int)Hh, (int)W, (float)crop_width, (float)crop_height, loss, record8);
     ART_HIP(hipGetLastError());
@@ -1094,8 +1102,8 @@ extern "C" int art_flux_crop_kl_loss_bwd(const float* flux, const float* target_
                                          void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, ground_truth, record8, B, Hh, W) || !grad_loss || !grad_flux || !workspace) return ART_EINVAL;
-    if (B == 0) return ART_OK;
     float* grad_crop = workspace;                      // [B,Hh,W]
     float* com3 = workspace + B * Hh * W;              // [B,3]
     float* gcom = com3 + 3 * B;                        // [B,2]
