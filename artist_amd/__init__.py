@@ -23,7 +23,7 @@ from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nu
 from .flux import (FocalSpotLoss, KLDivergenceLoss, PixelLoss, bitmap_coordinates_to_target_coordinates,  # noqa: F401
                    crop_and_kl_loss, crop_and_pixel_loss, crop_flux_distributions_around_center, get_center_of_mass)
 from .kinematics import Actuators, RigidBody  # noqa: F401
-from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, trace_rays  # noqa: F401
+from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, perform_canting, trace_rays  # noqa: F401
 from . import optim  # noqa: F401
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer, surface_regularization_terms  # noqa: F401
 from .raytracing import HeliostatRayTracer  # noqa: F401

@@ -120,6 +120,18 @@ _BY_EXTENSION_HEADER = {
 EXTENSION_SIGNATURES = {name: signature for table in _BY_EXTENSION_HEADER.values() for name, signature in table.items()}
 EXTENSION_HEADERS = {header: tuple(table) for header, table in _BY_EXTENSION_HEADER.items()}
 
+# Entry points of the headers under include/modules/: one table for the whole directory (a new module is a new header and a new
+# key here), compared with whatever headers the directory holds by tests/test_canting_host.py.
+_BY_MODULE_HEADER = {
+    "modules/artist_hip_canting.h": {
+        "art_cant_facets_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
+        "art_cant_facets_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    },
+}
+
+MODULE_SIGNATURES = {name: signature for table in _BY_MODULE_HEADER.values() for name, signature in table.items()}
+MODULE_HEADERS = {header: tuple(table) for header, table in _BY_MODULE_HEADER.items()}
+
 _LIB = None
 
 
@@ -135,9 +147,9 @@ def build(verbose: bool = False) -> pathlib.Path:
 
 
 def bind(handle: ctypes.CDLL, path) -> ctypes.CDLL:
-    """Give every entry point of ``SIGNATURES`` and ``EXTENSION_SIGNATURES`` its types on ``handle`` (a build of the library loaded from ``path``) and
-    check the ABI version."""
-    for name, (restype, argtypes) in {**SIGNATURES, **EXTENSION_SIGNATURES}.items():
+    """Give every entry point of ``SIGNATURES``, ``EXTENSION_SIGNATURES`` and ``MODULE_SIGNATURES`` its types on ``handle`` (a build of the
+    library loaded from ``path``) and check the ABI version."""
+    for name, (restype, argtypes) in {**SIGNATURES, **EXTENSION_SIGNATURES, **MODULE_SIGNATURES}.items():
         try:
             fn = getattr(handle, name)
         except AttributeError as exc:

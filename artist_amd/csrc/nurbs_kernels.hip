@@ -39,6 +39,7 @@
 
 #include "launch_common.hpp"
 #include "nurbs_basis.hpp"   // find_span, basis<> (A2.3), norm3 - shared with surface_fit_kernels.hip
+#include "canting_basis.hpp" // canting_basis (transforms.py:320-340) - shared with canting_kernels.hip
 
 namespace art {
 
@@ -62,22 +63,6 @@ struct NurbsArgs {
     int grid_mode;          // 1: look for a cartesian grid (tensor-product scheme), 0: scattered scheme only
     int lds_floats;         // dynamic LDS of the launch, in floats
 };
-
-// transforms.py:320-340.  B[0..2] = e, B[3..5] = n_ortho, B[6..8] = u.
-__device__ __forceinline__ void canting_basis(const float* cant, float* B)
-{
-    float ex = cant[0], ey = cant[1], ez = cant[2];
-    const float nx = cant[4], ny = cant[5], nz = cant[6];
-    const float ne = fmaxf(norm3(ex, ey, ez), 1e-12f);
-    ex = ex / ne; ey = ey / ne; ez = ez / ne;
-    float ux = ey * nz - ez * ny, uy = ez * nx - ex * nz, uz = ex * ny - ey * nx;
-    const float nu_ = fmaxf(norm3(ux, uy, uz), 1e-8f);
-    ux = ux / nu_; uy = uy / nu_; uz = uz / nu_;
-    float ox = uy * ez - uz * ey, oy = uz * ex - ux * ez, oz = ux * ey - uy * ex;
-    const float no = fmaxf(norm3(ox, oy, oz), 1e-8f);
-    ox = ox / no; oy = oy / no; oz = oz / no;
-    B[0] = ex; B[1] = ey; B[2] = ez; B[3] = ox; B[4] = oy; B[5] = oz; B[6] = ux; B[7] = uy; B[8] = uz;
-}
 
 // float index (even) at which the backward's double accumulator starts inside the dynamic LDS block
 __host__ __device__ inline int nurbs_f64_offset(const NurbsArgs& a)

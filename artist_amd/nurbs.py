@@ -114,8 +114,8 @@ class NURBSSurfaces(torch.nn.Module):
         nuq = self._unique_counts()
         if orientations is not None and orientations.requires_grad:
             raise ValueError("orientations that require grad go through artist_amd.align_surfaces, not the fused evaluation")
-        return ops.NurbsEval.apply(self.control_points, evaluation_points, self.knot_vectors_u, self.knot_vectors_v,
-                                   canting, facet_translations, p, q, bool(self.uniform), nuq[0], nuq[1], orientations)
+        return ops.nurbs_eval(self.control_points, evaluation_points, self.knot_vectors_u, self.knot_vectors_v,
+                              canting, facet_translations, p, q, bool(self.uniform), nuq[0], nuq[1], orientations)
 
     def forward(self, evaluation_points, canting, facet_translations, device=None):
         """Alias of :meth:`calculate_surface_points_and_normals` (artist/nurbs/surfaces.py:691-727)."""

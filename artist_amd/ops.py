@@ -17,7 +17,7 @@ from . import _lib
 
 __all__ = ["trace_rays", "nurbs_surface_points_and_normals", "per_target_sum", "align_surfaces", "TraceRays",
            "NurbsEval", "AlignSurfaces", "check_async_errors", "record_launch_events",
-           "sample_distortions"]
+           "sample_distortions", "CantFacets", "perform_canting", "nurbs_eval"]
 
 
 def _stream(device: torch.device) -> int:
@@ -471,7 +471,8 @@ class _PerTargetSum(torch.autograd.Function):
 
 class NurbsEval(torch.autograd.Function):
     """``NURBSSurfaces.calculate_surface_points_and_normals`` (artist/nurbs/surfaces.py:475-689),
-    differentiable w.r.t. the control points."""
+    differentiable w.r.t. the control points.  Canting and translations are constants of this fused launch: tensors that
+    require grad take :func:`nurbs_eval`, which routes them through :class:`CantFacets`."""
 
     @staticmethod
     def forward(ctx, control_points, eval_points, knots_u, knots_v, canting, translations, p, q, uniform,
@@ -525,14 +526,109 @@ class NurbsEval(torch.autograd.Function):
         return (g_cp,) + (None,) * 11
 
 
+class CantFacets(torch.autograd.Function):
+    """The canting rotation of ``points`` and ``normals`` ``[H,F,M,4]`` (either may be None) by the facet bases of ``canting``
+    ``[H,F,2,4]``, plus ``translations`` ``[H,F,4]`` (or None) on the points (artist/geometry/transforms.py:276-347,
+    artist/nurbs/surfaces.py:674-687; ``art_cant_facets_fwd`` / ``_bwd``, include/modules/artist_hip_canting.h).
+    Differentiable w.r.t. all four tensors; the backward is ONE launch that forms only the gradients asked for."""
+
+    @staticmethod
+    def forward(ctx, canting, translations, points, normals, inverse=False):
+        given = [t for t in (points, normals) if t is not None]
+        if not given:
+            raise ValueError("CantFacets needs points, normals or both")
+        dev = _require_cuda(canting, *given, *(() if translations is None else (translations,)))
+        data = given[0]
+        if data.dim() != 4 or data.shape[3] != 4 or any(t.shape != data.shape for t in given):
+            raise ValueError("points / normals must be [H,F,M,4] (and of one shape)")
+        H, F, M = int(data.shape[0]), int(data.shape[1]), int(data.shape[2])
+        if tuple(canting.shape) != (H, F, 2, 4):
+            raise ValueError(f"canting must be [{H},{F},2,4], got {tuple(canting.shape)}")
+        inverse = bool(inverse)
+        if translations is not None and (inverse or points is None):
+            raise ValueError("translations go with the points of a forward canting only")
+        cant = _f32c(canting)
+        tr = None if translations is None else _f32c(translations.reshape(H, F, 4))
+        pts = None if points is None else _f32c(points)
+        nrm = None if normals is None else _f32c(normals)
+        out_p = None if pts is None else torch.empty_like(pts)
+        out_n = None if nrm is None else torch.empty_like(nrm)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _timed_call("art_cant_facets_fwd", dev, cant.data_ptr(), ptr(tr), ptr(pts), ptr(nrm), 1 if inverse else 0, H * F, M,
+                    ptr(out_p), ptr(out_n))
+        # the data is read again only by the canting gradient
+        keep = ctx.needs_input_grad[0]
+        ctx.save_for_backward(cant, pts if keep else None, nrm if keep else None)
+        ctx.meta = (inverse, H, F, M, None if translations is None else tuple(translations.shape),
+                    points is not None, normals is not None)
+        ctx.set_materialize_grads(False)
+        return out_p, out_n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_p, g_n):
+        cant, pts, nrm = ctx.saved_tensors
+        inverse, H, F, M, tr_shape, has_p, has_n = ctx.meta
+        need_c, need_t, need_p, need_n = ctx.needs_input_grad[:4]
+        need_t = need_t and tr_shape is not None
+        need_p, need_n = need_p and has_p and g_p is not None, need_n and has_n and g_n is not None
+        if (g_p is None and g_n is None) or not (need_c or need_t or need_p or need_n):
+            return (None,) * 5
+        dev = cant.device
+        g_p = None if g_p is None else _f32c(g_p)
+        g_n = None if g_n is None else _f32c(g_n)
+        gd_p = torch.empty_like(g_p) if need_p else None
+        gd_n = torch.empty_like(g_n) if need_n else None
+        g_c = torch.empty_like(cant) if need_c else None
+        g_t = torch.empty((H, F, 4), dtype=torch.float32, device=dev) if need_t else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _timed_call("art_cant_facets_bwd", dev, cant.data_ptr(), ptr(pts) if g_p is not None else None,
+                    ptr(nrm) if g_n is not None else None, ptr(g_p), ptr(g_n), 1 if inverse else 0, H * F, M,
+                    ptr(gd_p), ptr(gd_n), ptr(g_c), ptr(g_t))
+        return g_c, None if g_t is None else g_t.reshape(tr_shape), gd_p, gd_n, None
+
+
+def perform_canting(canting_angles: torch.Tensor, data: torch.Tensor, inverse: bool = False,
+                    device: torch.device | None = None) -> torch.Tensor:
+    """``artist.geometry.transforms.perform_canting`` (transforms.py:276-347): ``data`` ``[H,F,M,4]`` rotated by the facet bases
+    of ``canting_angles`` ``[H,F,2,4]`` - ``data @ R^T``, or ``data @ R`` for ``inverse=True`` (decanting).  Differentiable
+    w.r.t. both tensors; fp32 on the GPU (``device`` = None: where ``data`` is)."""
+    if device is not None:
+        canting_angles, data = canting_angles.to(device), data.to(device)
+    return CantFacets.apply(canting_angles, None, data, None, bool(inverse))[0]
+
+
+def nurbs_eval(control_points, eval_points, knots_u, knots_v, canting, translations, p, q, uniform, n_unique_u, n_unique_v,
+               orientation=None):
+    """Surface points and normals by the route that reaches every tensor asking for a gradient.  Constants for canting and
+    translations: the one fused launch of :class:`NurbsEval`, as ever.  A canting or translation tensor that requires grad:
+    the same kernel without them, then :class:`CantFacets`, then :func:`align_surfaces` if ``orientation`` was given - the
+    same values bit for bit, and gradients for all three of control points, canting and translations."""
+    learns = canting is not None and torch.is_grad_enabled() and (
+        canting.requires_grad or (translations is not None and translations.requires_grad))
+    if not learns:
+        return NurbsEval.apply(control_points, eval_points, knots_u, knots_v, canting, translations, p, q, uniform,
+                               n_unique_u, n_unique_v, orientation)
+    if translations is None:
+        raise ValueError("facet_translations must be given with canting")
+    points, normals = NurbsEval.apply(control_points, eval_points, knots_u, knots_v, None, None, p, q, uniform,
+                                      n_unique_u, n_unique_v, None)
+    points, normals = CantFacets.apply(canting, translations, points, normals, False)
+    if orientation is not None:
+        shape = points.shape
+        points, normals = align_surfaces(points.reshape(shape[0], -1, 4), normals.reshape(shape[0], -1, 4), orientation.detach())
+        points, normals = points.reshape(shape), normals.reshape(shape)
+    return points, normals
+
+
 def nurbs_surface_points_and_normals(control_points, eval_points, knots_u, knots_v, degrees, canting=None,
                                      translations=None, uniform=True, n_unique=None, orientation=None):
     p, q = int(degrees[0]), int(degrees[1])
     nu, nv = control_points.shape[2], control_points.shape[3]
     if n_unique is None:
         n_unique = (nu - p + 1, nv - q + 1)
-    return NurbsEval.apply(control_points, eval_points, knots_u, knots_v, canting, translations, p, q,
-                           bool(uniform), int(n_unique[0]), int(n_unique[1]), orientation)
+    return nurbs_eval(control_points, eval_points, knots_u, knots_v, canting, translations, p, q,
+                      bool(uniform), int(n_unique[0]), int(n_unique[1]), orientation)
 
 
 class AlignSurfaces(torch.autograd.Function):
