@@ -23,19 +23,6 @@ namespace art {
 constexpr int kFluxBlock = 256;
 constexpr int kReduceBlock = kMomentsBlock;     // per-bitmap reductions: one workgroup per bitmap, 16 waves to hide latency
 
-__device__ __forceinline__ double block_sum(double v, double* s_red)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if (lane == 0) s_red[wave] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int w = 0; w < nw; ++w) r += s_red[w];
-    return r;
-}
-
 struct CropMap {       // pixel j of the output samples input coordinate ix(j); same arithmetic in every kernel
     float sx, sy, xc, yc;
     int W, Hh;
@@ -43,60 +30,89 @@ struct CropMap {       // pixel j of the output samples input coordinate ix(j); 
     __device__ __forceinline__ float iy(int i) const { return (((sy * lin11(i, Hh) + yc) + 1.0f) / 2.0f) * (float)(Hh - 1); }
 };
 
-__device__ __forceinline__ CropMap make_map(const float* __restrict__ dims, const float* __restrict__ com, int b, int W,
-                                            int Hh, float crop_w, float crop_h)
+__device__ __forceinline__ CropMap make_map(const float* __restrict__ dims, float xc, float yc, int b, int W, int Hh, float crop_w,
+                                            float crop_h)
 {
     CropMap m;
     m.sx = crop_w / fmaxf(dims[2 * b], 1e-8f);           // bitmap.py:218-225
     m.sy = crop_h / fmaxf(dims[2 * b + 1], 1e-8f);
-    m.xc = com[3 * b]; m.yc = com[3 * b + 1];
+    m.xc = xc; m.yc = yc;
     m.W = W; m.Hh = Hh;
     return m;
 }
 
-// com[b] = (x centre, y centre, sum + 1e-8) of bitmap b in normalised coordinates (:165-182).  One pass, sums in
-// fp64: sum x (f / S) and (sum x f) / S differ by far less than the fp32 rounding of the reference's own sums.
-__global__ __launch_bounds__(kReduceBlock) void flux_com_kernel(const float* __restrict__ flux, int Hh, int W,
-                                                              float* __restrict__ com)
+// com[b] = (x centre, y centre, sum + 1e-8) of bitmap b, one pass, sums in fp64: in normalised coordinates for the crop
+// (bitmap.py:165-182), or - get_center_of_mass (bitmap.py:12-71), what FocalSpotLoss (artist/optim/loss.py:124-250) and the
+// kinematics reconstructor's validation (kinematics_reconstructor.py:120) ask of the tracer's bitmaps - in PIXEL coordinates
+// (e, u) = sum_j j f / (sum f + 1e-8).
+template <typename Weights>
+__global__ __launch_bounds__(kReduceBlock) void flux_com_kernel(const float* __restrict__ flux, int Hh, int W, float* __restrict__ com)
 {
-    __shared__ double s_red[16];
+    __shared__ double s_red[16 * 3];
     const int b = blockIdx.x;
-    const float* __restrict__ f = flux + (int64_t)b * Hh * W;
-    double s = 0.0, xs = 0.0, ys = 0.0;
-    if ((W & 3) == 0) {
-        // four pixels of one row per load; (y, x) advanced without a division
-        const int W4 = W >> 2;
-        int x4 = threadIdx.x % W4, y = threadIdx.x / W4;
-        const int dx = blockDim.x % W4, dy = blockDim.x / W4;
-        const float4* __restrict__ f4 = reinterpret_cast<const float4*>(f);
-        for (int k = threadIdx.x; k < Hh * W4; k += blockDim.x) {
-            const float4 v = f4[k];
-            const int x = 4 * x4;
-            s += (double)((v.x + v.y) + (v.z + v.w));
-            xs += (double)((lin11(x, W) * v.x + lin11(x + 1, W) * v.y) + (lin11(x + 2, W) * v.z + lin11(x + 3, W) * v.w));
-            ys += (double)(lin11(y, Hh) * ((v.x + v.y) + (v.z + v.w)));
-            x4 += dx; y += dy;
-            if (x4 >= W4) { x4 -= W4; ++y; }
-        }
-    } else {
-        int x = threadIdx.x % W, y = threadIdx.x / W;
-        const int dx = blockDim.x % W, dy = blockDim.x / W;
-        for (int k = threadIdx.x; k < Hh * W; k += blockDim.x) {
-            const float v = f[k];
-            s += (double)v;
-            xs += (double)(lin11(x, W) * v);
-            ys += (double)(lin11(y, Hh) * v);
-            x += dx; y += dy;
-            if (x >= W) { x -= W; ++y; }
-        }
-    }
-    s = block_sum(s, s_red);
-    xs = block_sum(xs, s_red);
-    ys = block_sum(ys, s_red);
+    double a[3];
+    moment_sums<Weights>(flux + (int64_t)b * Hh * W, Hh, W, 0, Hh, s_red, a);
     if (threadIdx.x == 0) {
-        const float S = (float)s + 1e-8f;
-        com[3 * b] = (float)(xs / (double)S); com[3 * b + 1] = (float)(ys / (double)S); com[3 * b + 2] = S;
+        float xc, yc, S;
+        centre_from_sums(a[0], a[1], a[2], xc, yc, S);
+        com[3 * b] = xc; com[3 * b + 1] = yc; com[3 * b + 2] = S;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The bilinear sample of one output pixel (align_corners=True, zeros padding), in two halves because the map is separable: a
+// thread that stays in one column (the forward crop; the fused kernels when the workgroup size is a multiple of the bitmap
+// width: pixel k = tid + n * blockDim has j = tid % W) forms the column half once, and the row half is wave-uniform there.
+// ---------------------------------------------------------------------------------------------------
+struct CropAxis { int p0; float t; bool a, b; };      // first tap, weight of the second, which of the two lie in the bitmap
+__device__ __forceinline__ CropAxis crop_axis(float c, int n)
+{
+    CropAxis h;
+    const float c0 = floorf(c);
+    h.t = c - c0; h.p0 = (int)c0;
+    h.a = h.p0 >= 0 && h.p0 < n; h.b = h.p0 + 1 >= 0 && h.p0 + 1 < n;
+    return h;
+}
+__device__ __forceinline__ CropAxis crop_column(const CropMap& m, int j) { return crop_axis(m.ix(j), m.W); }
+__device__ __forceinline__ CropAxis crop_row(const CropMap& m, int i) { return crop_axis(m.iy(i), m.Hh); }
+
+// The sample of output pixel (i, column x): the sum of the present taps in this order (an absent tap adds nothing, not + 0), and
+// in `v` the four values (0 where a tap is absent) with the two weights, for whoever needs the sample's gradient.
+// `pixel(k)`: element k of the bitmap - from global memory, or from the rows a workgroup has staged in LDS.
+// (The row half is formed here and not handed in: as a local of the caller's loop it made the compiler unroll the fused KL kernels
+//  with a remainder loop - 63 and 68 registers instead of 41 and 45, the forward kernel one occupancy step down.)
+struct CropTaps { float v00, v01, v10, v11, tx, ty; };
+template <typename Pixel>
+__device__ __forceinline__ float crop_sample_from(Pixel&& pixel, const CropMap& m, const CropAxis& x, int i, CropTaps& v)
+{
+    const CropAxis y = crop_row(m, i);
+    const float ty = y.t;
+    v.tx = x.t; v.ty = ty;
+    v.v00 = y.a && x.a ? pixel(y.p0 * m.W + x.p0) : 0.0f; v.v01 = y.a && x.b ? pixel(y.p0 * m.W + x.p0 + 1) : 0.0f;
+    v.v10 = y.b && x.a ? pixel((y.p0 + 1) * m.W + x.p0) : 0.0f; v.v11 = y.b && x.b ? pixel((y.p0 + 1) * m.W + x.p0 + 1) : 0.0f;
+    float acc = 0.0f;
+    if (y.a && x.a) acc += v.v00 * ((1.0f - x.t) * (1.0f - ty));
+    if (y.a && x.b) acc += v.v01 * (x.t * (1.0f - ty));
+    if (y.b && x.a) acc += v.v10 * ((1.0f - x.t) * ty);
+    if (y.b && x.b) acc += v.v11 * (x.t * ty);
+    return acc;
+}
+__device__ __forceinline__ float crop_sample(const float* __restrict__ f, const CropMap& m, const CropAxis& x, int i, CropTaps& v)
+{
+    return crop_sample_from([&](int k) { return f[k]; }, m, x, i, v);
+}
+
+// d sample / d (ix, iy): grid_sample's gradient w.r.t. its grid, per pixel ...
+__device__ __forceinline__ void crop_sample_gradient(const CropTaps& v, float& gx, float& gy)
+{
+    gx = (v.v01 - v.v00) * (1.0f - v.ty) + (v.v11 - v.v10) * v.ty;
+    gy = (v.v10 - v.v00) * (1.0f - v.tx) + (v.v11 - v.v01) * v.tx;
+}
+// ... and, summed over a bitmap, through affine_grid's translation: the gradient of the two centre coordinates
+__device__ __forceinline__ void finish_centre_gradient(double gx, double gy, int W, int Hh, float* __restrict__ g2)
+{
+    g2[0] = (float)(gx * (double)((float)(W - 1) / 2.0f));
+    g2[1] = (float)(gy * (double)((float)(Hh - 1) / 2.0f));
 }
 
 // grid (ceil(W / 256), ceil(Hh / kCropRows), B): a thread walks kCropRows output pixels of one column (the column's
@@ -112,30 +128,17 @@ __global__ __launch_bounds__(kFluxBlock) void flux_crop_fwd_kernel(const float* 
     const int b = blockIdx.z;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= W) return;
-    const CropMap m = make_map(dims, com, b, W, Hh, crop_w, crop_h);
+    const CropMap m = make_map(dims, com[3 * b], com[3 * b + 1], b, W, Hh, crop_w, crop_h);
     const float* __restrict__ f = flux + (int64_t)b * Hh * W;
-    const float ix = m.ix(j);
-    const float x0f = floorf(ix);
-    const float tx = ix - x0f;
-    const int x0 = (int)x0f;
-    const bool xa = x0 >= 0 && x0 < W, xb = x0 + 1 >= 0 && x0 + 1 < W;
+    const CropAxis col = crop_column(m, j);
     const int i_end = min((int)(blockIdx.y + 1) * kCropRows, Hh);
     for (int i = blockIdx.y * kCropRows; i < i_end; ++i) {
-        const float iy = m.iy(i);
-        const float y0f = floorf(iy);
-        const float ty = iy - y0f;
-        const int y0 = (int)y0f;
-        const bool ya = y0 >= 0 && y0 < Hh, yb = y0 + 1 >= 0 && y0 + 1 < Hh;
-        float acc = 0.0f;
-        if (ya && xa) acc += f[y0 * W + x0] * ((1.0f - tx) * (1.0f - ty));
-        if (ya && xb) acc += f[y0 * W + x0 + 1] * (tx * (1.0f - ty));
-        if (yb && xa) acc += f[(y0 + 1) * W + x0] * ((1.0f - tx) * ty);
-        if (yb && xb) acc += f[(y0 + 1) * W + x0 + 1] * (tx * ty);
-        out[(int64_t)b * Hh * W + i * W + j] = acc;
+        CropTaps v;
+        out[(int64_t)b * Hh * W + i * W + j] = crop_sample(f, m, col, i, v);
     }
 }
 
-// gcom[b] = (dL/dxc, dL/dyc): grid_sample's gradient w.r.t. its grid, summed through affine_grid's translation
+// gcom[b] = (dL/dxc, dL/dyc)
 __global__ __launch_bounds__(kReduceBlock) void flux_crop_bwd_com_kernel(const float* __restrict__ flux,
                                                                        const float* __restrict__ dims,
                                                                        const float* __restrict__ com,
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_bwd_com_kernel(const f
 {
     __shared__ double s_red[16];
     const int b = blockIdx.x;
-    const CropMap m = make_map(dims, com, b, W, Hh, crop_w, crop_h);
+    const CropMap m = make_map(dims, com[3 * b], com[3 * b + 1], b, W, Hh, crop_w, crop_h);
     const float* __restrict__ f = flux + (int64_t)b * Hh * W;
     const float* __restrict__ g = grad_out + (int64_t)b * Hh * W;
     double gx = 0.0, gy = 0.0;
@@ -155,35 +158,30 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_bwd_com_kernel(const f
     constexpr int U = 4;
     const int npx = Hh * W;
     for (int k0 = threadIdx.x; k0 < npx; k0 += U * blockDim.x) {
-        float v00[U], v01[U], v10[U], v11[U], go[U], tx[U], ty[U];
+        CropTaps v[U];
+        float go[U];
 #pragma unroll
         for (int q = 0; q < U; ++q) {
             const int k = k0 + q * blockDim.x;
             const bool live = k < npx;
             const int i = live ? k / W : 0, j = live ? k - i * W : 0;
-            const float ix = m.ix(j), iy = m.iy(i);
-            const float x0f = floorf(ix), y0f = floorf(iy);
-            tx[q] = ix - x0f; ty[q] = iy - y0f;
-            const int x0 = (int)x0f, y0 = (int)y0f;
-            const bool xa = live && x0 >= 0 && x0 < W, xb = live && x0 + 1 >= 0 && x0 + 1 < W;
-            const bool ya = y0 >= 0 && y0 < Hh, yb = y0 + 1 >= 0 && y0 + 1 < Hh;
-            v00[q] = ya && xa ? f[y0 * W + x0] : 0.0f; v01[q] = ya && xb ? f[y0 * W + x0 + 1] : 0.0f;
-            v10[q] = yb && xa ? f[(y0 + 1) * W + x0] : 0.0f; v11[q] = yb && xb ? f[(y0 + 1) * W + x0 + 1] : 0.0f;
+            CropAxis col = crop_column(m, j);
+            col.a = live && col.a; col.b = live && col.b;           // (a trip's pixels past the end load nothing)
+            crop_sample(f, m, col, i, v[q]);
             go[q] = live ? g[k] : 0.0f;
         }
 #pragma unroll
         for (int q = 0; q < U; ++q) {
             if (k0 + q * (int)blockDim.x >= npx) break;
-            gx += (double)(go[q] * ((v01[q] - v00[q]) * (1.0f - ty[q]) + (v11[q] - v10[q]) * ty[q]));
-            gy += (double)(go[q] * ((v10[q] - v00[q]) * (1.0f - tx[q]) + (v11[q] - v01[q]) * tx[q]));
+            float sx, sy;
+            crop_sample_gradient(v[q], sx, sy);
+            gx += (double)(go[q] * sx);
+            gy += (double)(go[q] * sy);
         }
     }
     gx = block_sum(gx, s_red);
     gy = block_sum(gy, s_red);
-    if (threadIdx.x == 0) {
-        gcom[2 * b] = (float)(gx * (double)((float)(W - 1) / 2.0f));
-        gcom[2 * b + 1] = (float)(gy * (double)((float)(Hh - 1) / 2.0f));
-    }
+    if (threadIdx.x == 0) finish_centre_gradient(gx, gy, W, Hh, gcom + 2 * b);
 }
 
 // Weight with which output pixel `o` (sampling coordinate c = map(o)) read input pixel `p`.
@@ -217,25 +215,28 @@ __device__ __forceinline__ float gather_rows(const CropMap& m, const float* __re
     return acc;
 }
 
+// Candidate output indices whose sampling coordinate can lie within one pixel of input index `p`:
+// ix(j) = sx (j - (W-1)/2) + (xc + 1)(W-1)/2 up to rounding (<< 1e-3 pixel for bitmaps up to 32768 wide), so the candidates
+// are the j with |ix(j) - x| < 1 + 4e-3; tap() decides exactly
+__device__ __forceinline__ void tap_range(float scale, float centre, int n, int p, int& lo_i, int& hi_i)
+{
+    lo_i = 0; hi_i = n - 1;
+    if (scale > 1e-6f && scale < 1e6f) {
+        const float b = (centre + 1.0f) * 0.5f * (float)(n - 1) - scale * 0.5f * (float)(n - 1);
+        const float lo = ((float)p - 1.004f - b) / scale, hi = ((float)p + 1.004f - b) / scale;
+        if (lo > -2.0e9f && lo < 2.0e9f && hi > -2.0e9f && hi < 2.0e9f) { lo_i = max(0, (int)ceilf(lo)); hi_i = min(n - 1, (int)floorf(hi)); }
+    }
+}
+
 // Gradient of one INPUT pixel (x, y): direct part = sum over the output pixels that sampled it (the map is separable
 // and monotone, so they form a small index rectangle), plus the part through the centre of mass.  General form, any
 // crop scale; the tiled kernel below uses it for bitmaps whose scale needs more than four taps per axis.
 __device__ __forceinline__ float crop_bwd_pixel(const CropMap& m, const float* __restrict__ g, float S,
                                                 const float* __restrict__ gcom, int b, int Hh, int W, int x, int y)
 {
-    // ix(j) = sx (j - (W-1)/2) + (xc + 1)(W-1)/2 up to rounding (<< 1e-3 pixel for bitmaps up to 32768 wide):
-    // candidates j with |ix(j) - x| < 1 + 4e-3; tap() decides exactly
-    int j0 = 0, j1 = W - 1, i0 = 0, i1 = Hh - 1;
-    if (m.sx > 1e-6f && m.sx < 1e6f) {
-        const float bx = (m.xc + 1.0f) * 0.5f * (float)(W - 1) - m.sx * 0.5f * (float)(W - 1);
-        const float lo = ((float)x - 1.004f - bx) / m.sx, hi = ((float)x + 1.004f - bx) / m.sx;
-        if (lo > -2.0e9f && lo < 2.0e9f && hi > -2.0e9f && hi < 2.0e9f) { j0 = max(0, (int)ceilf(lo)); j1 = min(W - 1, (int)floorf(hi)); }
-    }
-    if (m.sy > 1e-6f && m.sy < 1e6f) {
-        const float by = (m.yc + 1.0f) * 0.5f * (float)(Hh - 1) - m.sy * 0.5f * (float)(Hh - 1);
-        const float lo = ((float)y - 1.004f - by) / m.sy, hi = ((float)y + 1.004f - by) / m.sy;
-        if (lo > -2.0e9f && lo < 2.0e9f && hi > -2.0e9f && hi < 2.0e9f) { i0 = max(0, (int)ceilf(lo)); i1 = min(Hh - 1, (int)floorf(hi)); }
-    }
+    int j0, j1, i0, i1;
+    tap_range(m.sx, m.xc, W, x, j0, j1);
+    tap_range(m.sy, m.yc, Hh, y, i0, i1);
     float acc = 0.0f;
     if (j1 - j0 < 4) acc = gather_rows<4>(m, g, W, x, y, j0, j1, i0, i1);
     else if (j1 - j0 < 8) acc = gather_rows<8>(m, g, W, x, y, j0, j1, i0, i1);
@@ -252,17 +253,6 @@ __device__ __forceinline__ float crop_bwd_pixel(const CropMap& m, const float* _
         }
     }
     return acc + gcom[2 * b] * (lin11(x, W) - m.xc) / S + gcom[2 * b + 1] * (lin11(y, Hh) - m.yc) / S;
-}
-
-// Candidate output indices whose sampling coordinate can lie within one pixel of input index `p` (see above).
-__device__ __forceinline__ void tap_range(float scale, float centre, int n, int p, int& lo_i, int& hi_i)
-{
-    lo_i = 0; hi_i = n - 1;
-    if (scale > 1e-6f && scale < 1e6f) {
-        const float b = (centre + 1.0f) * 0.5f * (float)(n - 1) - scale * 0.5f * (float)(n - 1);
-        const float lo = ((float)p - 1.004f - b) / scale, hi = ((float)p + 1.004f - b) / scale;
-        if (lo > -2.0e9f && lo < 2.0e9f && hi > -2.0e9f && hi < 2.0e9f) { lo_i = max(0, (int)ceilf(lo)); hi_i = min(n - 1, (int)floorf(hi)); }
-    }
 }
 
 // The same gradient organised by tiles of 64 x 32 input pixels: the map is separable, so the
@@ -282,7 +272,7 @@ __global__ __launch_bounds__(256) void flux_crop_bwd_tiled_kernel(const float* _
                                                                   const float* __restrict__ gcom,
                                                                   const float* __restrict__ grad_out, int Hh, int W,
                                                                   float crop_w, float crop_h, float* __restrict__ grad_flux,
-                                                                  const float* __restrict__ grad_loss, int grad_loss_stride = 1)
+                                                                  const float* __restrict__ grad_loss, int grad_loss_stride)
 {
     constexpr int CS = LOSS ? 4 : 3;                 // stride of the centre record
     __shared__ int s_j0[kTileX], s_i0[kTileY];
@@ -292,9 +282,7 @@ __global__ __launch_bounds__(256) void flux_crop_bwd_tiled_kernel(const float* _
     __shared__ float s_gy[kTileY];                   // the row's share of the centre-of-mass term (one division per row, not per pixel)
     const int b = blockIdx.z;
     const int x0 = blockIdx.x * kTileX, y0 = blockIdx.y * kTileY;
-    CropMap m;
-    m.sx = crop_w / fmaxf(dims[2 * b], 1e-8f); m.sy = crop_h / fmaxf(dims[2 * b + 1], 1e-8f);
-    m.xc = com[CS * b]; m.yc = com[CS * b + 1]; m.W = W; m.Hh = Hh;
+    const CropMap m = make_map(dims, com[CS * b], com[CS * b + 1], b, W, Hh, crop_w, crop_h);
     const float S = com[CS * b + 2];
     const float scale = LOSS ? (grad_loss[(int64_t)b * grad_loss_stride] * 2.0f) / com[CS * b + 3] : 1.0f;     // (stride 0: the gradient of a summed loss)
     if (threadIdx.x == 0) { s_wide = 0; s_ilo = 0x7fffffff; s_ihi = -1; }
@@ -336,6 +324,21 @@ __global__ __launch_bounds__(256) void flux_crop_bwd_tiled_kernel(const float* _
     //  that the loads of several rows are in flight together: with a branch per tap every load was waited for in turn
     //  and a workgroup took 26 us for 6 000 loads)
     const int xr = in_x ? 1 : 0;
+    auto horizontal_pass = [&](auto&& row_sum) {            // row_sum(row of g) = sum_q wx[q] row[j0 + q]
+        for (int r = threadIdx.x / kTileX; r <= ihi - ilo; r += kRowUnroll * (256 / kTileX)) {
+            float v[kRowUnroll];
+#pragma unroll
+            for (int q = 0; q < kRowUnroll; ++q) {
+                const int rr = min(r + q * (256 / kTileX), ihi - ilo);
+                v[q] = row_sum(g + (int64_t)(ilo + rr) * W);
+            }
+#pragma unroll
+            for (int q = 0; q < kRowUnroll; ++q) {
+                const int rr = r + q * (256 / kTileX);
+                if (rr <= ihi - ilo) s_t[rr][tx] = in_x ? v[q] : 0.0f;
+            }
+        }
+    };
     if (W >= 4) {
         // the four taps of a row are four consecutive floats: ONE 16-byte load at 4-byte alignment (from column min(j0, W - 4);
         // the weights move with it - absent taps carry weight 0 - so the non-zero products are added in the same order: same bits)
@@ -344,34 +347,14 @@ __global__ __launch_bounds__(256) void flux_crop_bwd_tiled_kernel(const float* _
         const float w0 = sh == 0 ? wx0 : 0.0f, w1 = sh == 0 ? wx1 : (sh == 1 ? wx0 : 0.0f);
         const float w2 = sh == 0 ? wx2 : (sh == 1 ? wx1 : (sh == 2 ? wx0 : 0.0f));
         const float w3 = sh == 0 ? wx3 : (sh == 1 ? wx2 : (sh == 2 ? wx1 : wx0));
-        for (int r = threadIdx.x / kTileX; r <= ihi - ilo; r += kRowUnroll * (256 / kTileX)) {
-            float v[kRowUnroll];
-#pragma unroll
-            for (int q = 0; q < kRowUnroll; ++q) {
-                const int rr = min(r + q * (256 / kTileX), ihi - ilo);
-                const Taps t = *reinterpret_cast<const Taps*>(g + (int64_t)(ilo + rr) * W + cb);
-                v[q] = ((t.t0 * w0 + t.t1 * w1) + t.t2 * w2) + t.t3 * w3;
-            }
-#pragma unroll
-            for (int q = 0; q < kRowUnroll; ++q) {
-                const int rr = r + q * (256 / kTileX);
-                if (rr <= ihi - ilo) s_t[rr][tx] = in_x ? v[q] : 0.0f;
-            }
-        }
-    } else
-    for (int r = threadIdx.x / kTileX; r <= ihi - ilo; r += kRowUnroll * (256 / kTileX)) {
-        float v[kRowUnroll];
-#pragma unroll
-        for (int q = 0; q < kRowUnroll; ++q) {
-            const int rr = min(r + q * (256 / kTileX), ihi - ilo);
-            const float* __restrict__ row = g + (int64_t)(ilo + rr) * W;
-            v[q] = ((row[c0 * xr] * wx0 + row[c1 * xr] * wx1) + row[c2 * xr] * wx2) + row[c3 * xr] * wx3;
-        }
-#pragma unroll
-        for (int q = 0; q < kRowUnroll; ++q) {
-            const int rr = r + q * (256 / kTileX);
-            if (rr <= ihi - ilo) s_t[rr][tx] = in_x ? v[q] : 0.0f;
-        }
+        horizontal_pass([&](const float* __restrict__ row) {
+            const Taps t = *reinterpret_cast<const Taps*>(row + cb);
+            return ((t.t0 * w0 + t.t1 * w1) + t.t2 * w2) + t.t3 * w3;
+        });
+    } else {
+        horizontal_pass([&](const float* __restrict__ row) {
+            return ((row[c0 * xr] * wx0 + row[c1 * xr] * wx1) + row[c2 * xr] * wx2) + row[c3 * xr] * wx3;
+        });
     }
     __syncthreads();
     if (!in_x) return;
@@ -412,6 +395,30 @@ __device__ __forceinline__ void for_each_pair(const float* __restrict__ p, const
     }
 }
 
+// KLDivergenceLoss (loss.py:385-410) of a prediction p against a truth g, both L1-normalised with a clamped norm:
+// sum_k exp(t_k) (t_k - q_k) with t = log(g / dg + eps), q = log(p / dp + eps).  `term` adds a pixel's share of the loss and of
+// dot = sum_k a_k p_k, a_k = -exp(t_k) / (p_k / dp + eps); `gradient` is gl dKL/dp_k, the second part through the norm of p.
+struct KlNorms {
+    static constexpr float eps = 1e-12f;
+    float npf, ngf, dp, dg;
+    __device__ __forceinline__ KlNorms(float np_, float ng_) : npf(np_), ngf(ng_), dp(fmaxf(np_, eps)), dg(fmaxf(ng_, eps)) {}
+    __device__ __forceinline__ void term(float pk, float gk, double& acc, double& dot) const
+    {
+        const float t = logf(gk / dg + eps), q = logf(pk / dp + eps);
+        const float et = expf(t);
+        acc += (double)(et * (t - q));
+        dot += (double)((-et / (pk / dp + eps)) * pk);
+    }
+    __device__ __forceinline__ float gradient(float pk, float gk, float dotf, float gl) const
+    {
+        const float t = logf(gk / dg + eps);
+        const float a = -expf(t) / (pk / dp + eps);
+        const float sgn = pk > 0.0f ? 1.0f : (pk < 0.0f ? -1.0f : 0.0f);
+        const float through_norm = npf > eps ? sgn * dotf / (dp * dp) : 0.0f;
+        return gl * (a / dp - through_norm);
+    }
+};
+
 __global__ __launch_bounds__(kReduceBlock) void flux_loss_kernel(const float* __restrict__ pred, const float* __restrict__ truth,
                                                                int64_t npix, int mode, float* __restrict__ loss,
                                                                const float* __restrict__ grad_loss,
@@ -434,94 +441,19 @@ __global__ __launch_bounds__(kReduceBlock) void flux_loss_kernel(const float* __
         }
         return;
     }
-    const float eps = 1e-12f;                                  // loss.py:385-410
     double np_ = 0.0, ng = 0.0;
     for_each_pair(p, g, npix, [&](int64_t, float pk, float gk) { np_ += (double)fabsf(pk); ng += (double)fabsf(gk); });
     const float npf = (float)block_sum(np_, s_red), ngf = (float)block_sum(ng, s_red);
-    const float dp = fmaxf(npf, eps), dg = fmaxf(ngf, eps);
+    const KlNorms kl(npf, ngf);
     double acc = 0.0, dot = 0.0;
-    for_each_pair(p, g, npix, [&](int64_t, float pk, float gk) {
-        const float t = logf(gk / dg + eps), q = logf(pk / dp + eps);
-        const float et = expf(t);
-        acc += (double)(et * (t - q));
-        dot += (double)((-et / (pk / dp + eps)) * pk);
-    });
+    for_each_pair(p, g, npix, [&](int64_t, float pk, float gk) { kl.term(pk, gk, acc, dot); });
     acc = block_sum(acc, s_red);
     const float dotf = (float)block_sum(dot, s_red);
     if (threadIdx.x == 0 && loss) loss[b] = (float)acc;
     if (gp) {
         const float gl = grad_loss[b];
-        for_each_pair(p, g, npix, [&](int64_t k, float pk, float gk) {
-            const float t = logf(gk / dg + eps);
-            const float a = -expf(t) / (pk / dp + eps);
-            const float sgn = pk > 0.0f ? 1.0f : (pk < 0.0f ? -1.0f : 0.0f);
-            const float through_norm = npf > eps ? sgn * dotf / (dp * dp) : 0.0f;
-            gp[k] = gl * (a / dp - through_norm);
-        });
+        for_each_pair(p, g, npix, [&](int64_t k, float pk, float gk) { gp[k] = kl.gradient(pk, gk, dotf, gl); });
     }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Sampling helpers of the fused crop + loss kernels (the arithmetic of flux_crop_fwd_kernel, tap for tap).
-// ---------------------------------------------------------------------------------------------------
-struct CropTap { int x0, y0; float tx, ty; bool xa, xb, ya, yb; };
-__device__ __forceinline__ float crop_sample(const float* __restrict__ f, const CropMap& m, int i, int j, float& v00, float& v01,
-                                             float& v10, float& v11, float& tx, float& ty)
-{
-    const float ix = m.ix(j), iy = m.iy(i);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    tx = ix - x0f; ty = iy - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    const bool xa = x0 >= 0 && x0 < m.W, xb = x0 + 1 >= 0 && x0 + 1 < m.W;
-    const bool ya = y0 >= 0 && y0 < m.Hh, yb = y0 + 1 >= 0 && y0 + 1 < m.Hh;
-    v00 = ya && xa ? f[y0 * m.W + x0] : 0.0f; v01 = ya && xb ? f[y0 * m.W + x0 + 1] : 0.0f;
-    v10 = yb && xa ? f[(y0 + 1) * m.W + x0] : 0.0f; v11 = yb && xb ? f[(y0 + 1) * m.W + x0 + 1] : 0.0f;
-    // the accumulation order of flux_crop_fwd_kernel (absent taps add nothing there either)
-    float acc = 0.0f;
-    if (ya && xa) acc += v00 * ((1.0f - tx) * (1.0f - ty));
-    if (ya && xb) acc += v01 * (tx * (1.0f - ty));
-    if (yb && xa) acc += v10 * ((1.0f - tx) * ty);
-    if (yb && xb) acc += v11 * (tx * ty);
-    return acc;
-}
-
-
-// The same sample with the column's part of the work done once per thread: when the workgroup size is a multiple of
-// the bitmap width a thread stays in ONE column (pixel k = tid + n * blockDim: j = tid % W, i = tid / W + n * blockDim / W),
-// so ix(j), its floor, weights and bounds leave the loop, and the row's iy(i) is wave-uniform.
-struct CropColumn { int x0; float tx; bool xa, xb; };
-__device__ __forceinline__ CropColumn crop_column(const CropMap& m, int j)
-{
-    CropColumn c;
-    const float ix = m.ix(j);
-    const float x0f = floorf(ix);
-    c.tx = ix - x0f; c.x0 = (int)x0f;
-    c.xa = c.x0 >= 0 && c.x0 < m.W; c.xb = c.x0 + 1 >= 0 && c.x0 + 1 < m.W;
-    return c;
-}
-// (`pixel(k)`: element k of the bitmap - from global memory, or from the rows a workgroup has staged in LDS)
-template <typename Pixel>
-__device__ __forceinline__ float crop_sample_col_from(Pixel&& pixel, const CropMap& m, const CropColumn& c, int i, float& v00,
-                                                      float& v01, float& v10, float& v11, float& ty)
-{
-    const float iy = m.iy(i);
-    const float y0f = floorf(iy);
-    ty = iy - y0f;
-    const int y0 = (int)y0f;
-    const bool ya = y0 >= 0 && y0 < m.Hh, yb = y0 + 1 >= 0 && y0 + 1 < m.Hh;
-    v00 = ya && c.xa ? pixel(y0 * m.W + c.x0) : 0.0f; v01 = ya && c.xb ? pixel(y0 * m.W + c.x0 + 1) : 0.0f;
-    v10 = yb && c.xa ? pixel((y0 + 1) * m.W + c.x0) : 0.0f; v11 = yb && c.xb ? pixel((y0 + 1) * m.W + c.x0 + 1) : 0.0f;
-    float acc = 0.0f;
-    if (ya && c.xa) acc += v00 * ((1.0f - c.tx) * (1.0f - ty));
-    if (ya && c.xb) acc += v01 * (c.tx * (1.0f - ty));
-    if (yb && c.xa) acc += v10 * ((1.0f - c.tx) * ty);
-    if (yb && c.xb) acc += v11 * (c.tx * ty);
-    return acc;
-}
-__device__ __forceinline__ float crop_sample_col(const float* __restrict__ f, const CropMap& m, const CropColumn& c, int i, float& v00,
-                                                 float& v01, float& v10, float& v11, float& ty)
-{
-    return crop_sample_col_from([&](int k) { return f[k]; }, m, c, i, v00, v01, v10, v11, ty);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -551,9 +483,9 @@ __global__ __launch_bounds__(kReduceBlock) void flux_com_parts_kernel(const floa
     const int b = blockIdx.y;
     const float* __restrict__ f = flux + (int64_t)b * Hh * W;
     for (int v = blockIdx.x * parts_per_wg; v < (int)(blockIdx.x + 1) * parts_per_wg; ++v) {
-        double s, xs, ys;
-        com_part_sums(f, Hh, W, v, s_red, s, xs, ys);
-        if (threadIdx.x == 0) { ws->com[b][v][0] = s; ws->com[b][v][1] = xs; ws->com[b][v][2] = ys; }
+        double a[3];
+        com_part_sums(f, Hh, W, v, s_red, a);
+        if (threadIdx.x == 0) { ws->com[b][v][0] = a[0]; ws->com[b][v][1] = a[1]; ws->com[b][v][2] = a[2]; }
     }
 }
 
@@ -562,8 +494,7 @@ __device__ __forceinline__ void com_from_parts(const double (*parts)[3], float& 
 {
     double s = 0.0, xs = 0.0, ys = 0.0;
     for (int v = 0; v < kLossParts; ++v) { s += parts[v][0]; xs += parts[v][1]; ys += parts[v][2]; }
-    S = (float)s + 1e-8f;
-    xc = (float)(xs / (double)S); yc = (float)(ys / (double)S);
+    centre_from_sums(s, xs, ys, xc, yc, S);
 }
 
 // loss, the record the backward pass reads and - with a residual - the centre's gradient per unit of 2 gl / sum(truth)
@@ -575,10 +506,7 @@ __device__ __forceinline__ void loss_from_parts(const double (*acc)[4], float xc
     const float sgf = (float)sg;
     loss[b] = (float)se / sgf;                              // loss.py:312-318
     com4[4 * b] = xc; com4[4 * b + 1] = yc; com4[4 * b + 2] = S; com4[4 * b + 3] = sgf;
-    if (gunit) {
-        gunit[2 * b] = (float)(gx * (double)((float)(W - 1) / 2.0f));
-        gunit[2 * b + 1] = (float)(gy * (double)((float)(Hh - 1) / 2.0f));
-    }
+    if (gunit) finish_centre_gradient(gx, gy, W, Hh, gunit + 2 * b);
 }
 
 template <bool WHOLE>       // WHOLE: one workgroup per bitmap does all four parts, the centre and the final sums itself
@@ -598,30 +526,28 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_pixel_loss_fwd_kernel(
     const float* __restrict__ f = flux + (int64_t)b * Hh * W;
     const float* __restrict__ g = truth + (int64_t)b * Hh * W;
     float* __restrict__ res = residual ? residual + (int64_t)b * Hh * W : nullptr;
-    CropMap m;
-    float S;
+    float xc, yc, S;
     if (moments != nullptr) {          // the sums came with the bitmaps (the trace's conversion pass formed them: flux_moments.hpp)
-        com_from_parts(reinterpret_cast<const double(*)[3]>(moments + (int64_t)b * kLossParts * 3), m.xc, m.yc, S);
+        com_from_parts(reinterpret_cast<const double(*)[3]>(moments + (int64_t)b * kLossParts * 3), xc, yc, S);
     } else if constexpr (WHOLE) {
         for (int v = 0; v < kLossParts; ++v) {
-            double s, xs, ys;
-            com_part_sums(f, Hh, W, v, s_red, s, xs, ys);
-            if (threadIdx.x == 0) { s_com[v][0] = s; s_com[v][1] = xs; s_com[v][2] = ys; }
+            double a[3];
+            com_part_sums(f, Hh, W, v, s_red, a);
+            if (threadIdx.x == 0) { s_com[v][0] = a[0]; s_com[v][1] = a[1]; s_com[v][2] = a[2]; }
         }
         __syncthreads();
-        com_from_parts(s_com, m.xc, m.yc, S);
+        com_from_parts(s_com, xc, yc, S);
     } else {
-        com_from_parts(ws->com[b], m.xc, m.yc, S);
+        com_from_parts(ws->com[b], xc, yc, S);
     }
-    m.sx = crop_w / fmaxf(dims[2 * b], 1e-8f); m.sy = crop_h / fmaxf(dims[2 * b + 1], 1e-8f);
-    m.W = W; m.Hh = Hh;
+    const CropMap m = make_map(dims, xc, yc, b, W, Hh, crop_w, crop_h);
     for (int v = blockIdx.x * parts_per_wg; v < (int)(blockIdx.x + 1) * parts_per_wg; ++v) {
         int r0, r1;
         part_rows(Hh, v, r0, r1);
         double a[4] = {0.0, 0.0, 0.0, 0.0};             // sum d^2, sum truth, and the two sums of the centre's gradient
         if ((int)blockDim.x % W == 0) {                 // a thread owns one column
             const int j = threadIdx.x % W, di = blockDim.x / W;
-            const CropColumn col = crop_column(m, j);
+            const CropAxis col = crop_column(m, j);
             // The bitmap rows this part's output rows sample, staged in LDS with 16-byte loads when they fit (stage_rows of them:
             // the launch's dynamic LDS): the four taps of a pixel are then LDS reads - a fifth of the vector-memory instructions
             // (four predicated 4-byte taps per pixel were four tag look-ups of the same two cache lines per wave): 0.298 -> 0.257 ms
@@ -645,11 +571,10 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_pixel_loss_fwd_kernel(
 #pragma unroll
                 for (int u = 0; u < kRows; ++u) {
                     const int i = min(i0 + u * di, r1 - 1);                 // (a clamped row is loaded and not used)
-                    float v00, v01, v10, v11, ty;
-                    c[u] = crop_sample_col_from(pixel, m, col, i, v00, v01, v10, v11, ty);
+                    CropTaps v;
+                    c[u] = crop_sample_from(pixel, m, col, i, v);
                     t[u] = g[i * W + j];
-                    gxs[u] = (v01 - v00) * (1.0f - ty) + (v11 - v10) * ty;
-                    gys[u] = (v10 - v00) * (1.0f - col.tx) + (v11 - v01) * col.tx;
+                    crop_sample_gradient(v, gxs[u], gys[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < kRows; ++u) {
@@ -679,15 +604,17 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_pixel_loss_fwd_kernel(
         } else {
             for (int k = r0 * W + threadIdx.x; k < r1 * W; k += blockDim.x) {
                 const int i = k / W, j = k - i * W;
-                float v00, v01, v10, v11, tx, ty;
-                const float c = crop_sample(f, m, i, j, v00, v01, v10, v11, tx, ty);
+                CropTaps v;
+                const float c = crop_sample(f, m, crop_column(m, j), i, v);
                 const float t = g[k];
                 const float d = c - t;
                 a[0] += (double)(d * d); a[1] += (double)t;
                 if (res) {
+                    float gxs, gys;
+                    crop_sample_gradient(v, gxs, gys);
                     res[k] = d;
-                    a[2] += (double)(d * ((v01 - v00) * (1.0f - ty) + (v11 - v10) * ty));
-                    a[3] += (double)(d * ((v10 - v00) * (1.0f - tx) + (v11 - v01) * tx));
+                    a[2] += (double)(d * gxs);
+                    a[3] += (double)(d * gys);
                 }
             }
         }
@@ -698,7 +625,7 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_pixel_loss_fwd_kernel(
         }
     }
     if constexpr (WHOLE) {
-        if (threadIdx.x == 0) loss_from_parts(s_acc, m.xc, m.yc, S, b, Hh, W, loss, com4, gunit);     // (its own writes)
+        if (threadIdx.x == 0) loss_from_parts(s_acc, xc, yc, S, b, Hh, W, loss, com4, gunit);     // (its own writes)
     }
 }
 
@@ -714,38 +641,7 @@ __global__ __launch_bounds__(256) void flux_crop_pixel_loss_final_kernel(const P
     loss_from_parts(ws->acc[b], xc, yc, S, b, Hh, W, loss, com4, gunit);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// get_center_of_mass (artist/flux/bitmap.py:12-71): PIXEL coordinates (e, u) of each bitmap's centre of mass,
-// sum_j j f / (sum f + 1e-8) - what FocalSpotLoss (artist/optim/loss.py:124-250) and the kinematics reconstructor's
-// validation (kinematics_reconstructor.py:120) ask of the tracer's bitmaps.  com[b] = (e px, u px, sum + 1e-8).
-// One streaming pass, fp64 sums; backward = one elementwise pass: d e_com / d f_ij = (j - e_com) / (S + 1e-8).
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kReduceBlock) void flux_com_px_kernel(const float* __restrict__ flux, int Hh, int W,
-                                                                 float* __restrict__ com)
-{
-    __shared__ double s_red[16];
-    const int b = blockIdx.x;
-    const float* __restrict__ f = flux + (int64_t)b * Hh * W;
-    double s = 0.0, xs = 0.0, ys = 0.0;
-    int x = threadIdx.x % W, y = threadIdx.x / W;
-    const int dx = blockDim.x % W, dy = blockDim.x / W;
-    for (int k = threadIdx.x; k < Hh * W; k += blockDim.x) {
-        const float v = f[k];
-        s += (double)v;
-        xs += (double)((float)x * v);
-        ys += (double)((float)y * v);
-        x += dx; y += dy;
-        if (x >= W) { x -= W; ++y; }
-    }
-    s = block_sum(s, s_red);
-    xs = block_sum(xs, s_red);
-    ys = block_sum(ys, s_red);
-    if (threadIdx.x == 0) {
-        const float S = (float)s + 1e-8f;
-        com[3 * b] = (float)(xs / (double)S); com[3 * b + 1] = (float)(ys / (double)S); com[3 * b + 2] = S;
-    }
-}
-
+// get_center_of_mass backward, one elementwise pass: d e_com / d f_ij = (j - e_com) / (S + 1e-8)
 __global__ __launch_bounds__(kFluxBlock) void flux_com_px_bwd_kernel(const float* __restrict__ com, const float* __restrict__ grad_com,
                                                                      int Hh, int W, float* __restrict__ grad_flux)
 {
@@ -759,69 +655,31 @@ __global__ __launch_bounds__(kFluxBlock) void flux_com_px_bwd_kernel(const float
 
 // ---------------------------------------------------------------------------------------------------
 // Fused crop around the centre of mass + KLDivergenceLoss (artist/flux/bitmap.py:121-246 followed by
-// artist/optim/loss.py:321-410 with the reduction over the two bitmap dimensions), one workgroup per bitmap, the same
-// arithmetic as flux_com_kernel / flux_crop_fwd_kernel / flux_loss_kernel(mode 1): the cropped bitmap never reaches
-// HBM.  The KL terms need the crop's L1 norm first, so the crop is sampled twice (the taps hit L2: the workgroup has
-// just streamed the bitmap).  rec8[b] = (x centre, y centre, sum + 1e-8, |crop|_1, |truth|_1, dot, 0, 0) for the
-// backward pass, where dot = sum_k a_k crop_k with a_k = -exp(t_k) / (crop_k / dp + eps).
+// artist/optim/loss.py:321-410 with the reduction over the two bitmap dimensions), one workgroup per bitmap: the cropped
+// bitmap never reaches HBM.  The KL terms need the crop's L1 norm first, so the crop is sampled twice (the taps hit L2: the
+// workgroup has just streamed the bitmap).  rec8[b] = (x centre, y centre, sum + 1e-8, |crop|_1, |truth|_1, dot, 0, 0) for
+// the backward pass (dot: see KlNorms).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void block_com(const float* __restrict__ f, int Hh, int W, double* s_red, float* s_com)
-{
-    double s = 0.0, xs = 0.0, ys = 0.0;
-    if ((W & 3) == 0) {                                 // flux_com_kernel's loop
-        const int W4 = W >> 2;
-        int x4 = threadIdx.x % W4, y = threadIdx.x / W4;
-        const int dx = blockDim.x % W4, dy = blockDim.x / W4;
-        const float4* __restrict__ f4 = reinterpret_cast<const float4*>(f);
-#pragma unroll 4
-        for (int k = threadIdx.x; k < Hh * W4; k += blockDim.x) {
-            const float4 v = f4[k];
-            const int x = 4 * x4;
-            s += (double)((v.x + v.y) + (v.z + v.w));
-            xs += (double)((lin11(x, W) * v.x + lin11(x + 1, W) * v.y) + (lin11(x + 2, W) * v.z + lin11(x + 3, W) * v.w));
-            ys += (double)(lin11(y, Hh) * ((v.x + v.y) + (v.z + v.w)));
-            x4 += dx; y += dy;
-            if (x4 >= W4) { x4 -= W4; ++y; }
-        }
-    } else {
-        int x = threadIdx.x % W, y = threadIdx.x / W;
-        const int dx = blockDim.x % W, dy = blockDim.x / W;
-        for (int k = threadIdx.x; k < Hh * W; k += blockDim.x) {
-            const float v = f[k];
-            s += (double)v; xs += (double)(lin11(x, W) * v); ys += (double)(lin11(y, Hh) * v);
-            x += dx; y += dy;
-            if (x >= W) { x -= W; ++y; }
-        }
-    }
-    s = block_sum(s, s_red); xs = block_sum(xs, s_red); ys = block_sum(ys, s_red);
-    if (threadIdx.x == 0) {
-        const float S = (float)s + 1e-8f;
-        s_com[0] = (float)(xs / (double)S); s_com[1] = (float)(ys / (double)S); s_com[2] = S;
-    }
-    __syncthreads();
-}
-
-// f(k, crop_k, v00, v01, v10, v11, tx, ty) for every output pixel k of the crop of bitmap `f`, each thread in its own
-// fixed order (a thread owns one column when the workgroup size is a multiple of the bitmap width)
+// fn(k, crop_k, its taps) for every output pixel k of the crop of bitmap `f`, each thread in its own fixed order
+// (a thread owns one column when the workgroup size is a multiple of the bitmap width)
 template <typename F>
 __device__ __forceinline__ void for_each_crop_pixel(const float* __restrict__ f, const CropMap& m, F&& fn)
 {
     const int W = m.W, Hh = m.Hh;
+    auto pixel = [&](int k, int i, const CropAxis& col) {
+        CropTaps v;
+        const float c = crop_sample(f, m, col, i, v);
+        fn(k, c, v);
+    };
     if ((int)blockDim.x % W == 0) {
         const int j = threadIdx.x % W, di = blockDim.x / W;
-        const CropColumn col = crop_column(m, j);
+        const CropAxis col = crop_column(m, j);
 #pragma unroll 4
-        for (int i = threadIdx.x / W; i < Hh; i += di) {
-            float v00, v01, v10, v11, ty;
-            const float c = crop_sample_col(f, m, col, i, v00, v01, v10, v11, ty);
-            fn(i * W + j, c, v00, v01, v10, v11, col.tx, ty);
-        }
+        for (int i = threadIdx.x / W; i < Hh; i += di) pixel(i * W + j, i, col);
     } else {
         for (int k = threadIdx.x; k < Hh * W; k += blockDim.x) {
             const int i = k / W, j = k - i * W;
-            float v00, v01, v10, v11, tx, ty;
-            const float c = crop_sample(f, m, i, j, v00, v01, v10, v11, tx, ty);
-            fn(k, c, v00, v01, v10, v11, tx, ty);
+            pixel(k, i, crop_column(m, j));
         }
     }
 }
@@ -832,35 +690,29 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_kl_loss_fwd_kernel(con
                                                                             float crop_w, float crop_h, float* __restrict__ loss,
                                                                             float* __restrict__ rec8)
 {
-    __shared__ double s_red[16];
+    __shared__ double s_red[16 * 3];
     __shared__ float s_com[3];
     const int b = blockIdx.x;
     const float* __restrict__ f = flux + (int64_t)b * Hh * W;
     const float* __restrict__ g = truth + (int64_t)b * Hh * W;
-    block_com(f, Hh, W, s_red, s_com);
-    CropMap m;
-    m.sx = crop_w / fmaxf(dims[2 * b], 1e-8f); m.sy = crop_h / fmaxf(dims[2 * b + 1], 1e-8f);
-    m.xc = s_com[0]; m.yc = s_com[1]; m.W = W; m.Hh = Hh;
-    const float eps = 1e-12f;                                  // loss.py:385-410, as flux_loss_kernel mode 1
+    double sums[3];
+    moment_sums<NormalisedWeights>(f, Hh, W, 0, Hh, s_red, sums);
+    if (threadIdx.x == 0) centre_from_sums(sums[0], sums[1], sums[2], s_com[0], s_com[1], s_com[2]);     // (two fp64 divisions: one thread)
+    __syncthreads();
+    const float xc = s_com[0], yc = s_com[1], S = s_com[2];
+    const CropMap m = make_map(dims, xc, yc, b, W, Hh, crop_w, crop_h);
     double np_ = 0.0, ng = 0.0;
-    for_each_crop_pixel(f, m, [&](int k, float c, float, float, float, float, float, float) {
-        np_ += (double)fabsf(c); ng += (double)fabsf(g[k]);
-    });
+    for_each_crop_pixel(f, m, [&](int k, float c, const CropTaps&) { np_ += (double)fabsf(c); ng += (double)fabsf(g[k]); });
     const float npf = (float)block_sum(np_, s_red), ngf = (float)block_sum(ng, s_red);
-    const float dp = fmaxf(npf, eps), dg = fmaxf(ngf, eps);
+    const KlNorms kl(npf, ngf);
     double acc = 0.0, dot = 0.0;
-    for_each_crop_pixel(f, m, [&](int k, float c, float, float, float, float, float, float) {
-        const float t = logf(g[k] / dg + eps), q = logf(c / dp + eps);
-        const float et = expf(t);
-        acc += (double)(et * (t - q));
-        dot += (double)((-et / (c / dp + eps)) * c);
-    });
+    for_each_crop_pixel(f, m, [&](int k, float c, const CropTaps&) { kl.term(c, g[k], acc, dot); });
     acc = block_sum(acc, s_red);
     const float dotf = (float)block_sum(dot, s_red);
     if (threadIdx.x == 0) {
         loss[b] = (float)acc;
         float* r = rec8 + 8 * b;
-        r[0] = s_com[0]; r[1] = s_com[1]; r[2] = s_com[2]; r[3] = npf; r[4] = ngf; r[5] = dotf; r[6] = 0.0f; r[7] = 0.0f;
+        r[0] = xc; r[1] = yc; r[2] = S; r[3] = npf; r[4] = ngf; r[5] = dotf; r[6] = 0.0f; r[7] = 0.0f;
     }
 }
 
@@ -880,28 +732,22 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_kl_loss_bwd_kernel(con
     const float* __restrict__ g = truth + (int64_t)b * Hh * W;
     float* __restrict__ gc = grad_crop + (int64_t)b * Hh * W;
     const float* r = rec8 + 8 * b;
-    CropMap m;
-    m.sx = crop_w / fmaxf(dims[2 * b], 1e-8f); m.sy = crop_h / fmaxf(dims[2 * b + 1], 1e-8f);
-    m.xc = r[0]; m.yc = r[1]; m.W = W; m.Hh = Hh;
-    const float eps = 1e-12f;
-    const float npf = r[3], ngf = r[4], dotf = r[5], gl = grad_loss[b];
-    const float dp = fmaxf(npf, eps), dg = fmaxf(ngf, eps);
+    const CropMap m = make_map(dims, r[0], r[1], b, W, Hh, crop_w, crop_h);
+    const KlNorms kl(r[3], r[4]);
+    const float dotf = r[5], gl = grad_loss[b];
     double gx = 0.0, gy = 0.0;
-    for_each_crop_pixel(f, m, [&](int k, float c, float v00, float v01, float v10, float v11, float tx, float ty) {
-        const float t = logf(g[k] / dg + eps);                    // flux_loss_kernel's gradient (mode 1)
-        const float a = -expf(t) / (c / dp + eps);
-        const float sgn = c > 0.0f ? 1.0f : (c < 0.0f ? -1.0f : 0.0f);
-        const float through_norm = npf > eps ? sgn * dotf / (dp * dp) : 0.0f;
-        const float go = gl * (a / dp - through_norm);
+    for_each_crop_pixel(f, m, [&](int k, float c, const CropTaps& v) {
+        const float go = kl.gradient(c, g[k], dotf, gl);
+        float sx, sy;
+        crop_sample_gradient(v, sx, sy);
         gc[k] = go;
-        gx += (double)(go * ((v01 - v00) * (1.0f - ty) + (v11 - v10) * ty));     // flux_crop_bwd_com_kernel
-        gy += (double)(go * ((v10 - v00) * (1.0f - tx) + (v11 - v01) * tx));
+        gx += (double)(go * sx);
+        gy += (double)(go * sy);
     });
     gx = block_sum(gx, s_red);
     gy = block_sum(gy, s_red);
     if (threadIdx.x == 0) {
-        gcom[2 * b] = (float)(gx * (double)((float)(W - 1) / 2.0f));
-        gcom[2 * b + 1] = (float)(gy * (double)((float)(Hh - 1) / 2.0f));
+        finish_centre_gradient(gx, gy, W, Hh, gcom + 2 * b);
         com3[3 * b] = m.xc; com3[3 * b + 1] = m.yc; com3[3 * b + 2] = r[2];
     }
 }
@@ -947,6 +793,17 @@ static int loss_workgroups_per_bitmap(int64_t B, int64_t Hh)
     return 4 * B <= cus ? 4 : (2 * B <= cus ? 2 : 1);
 }
 
+template <bool LOSS>        // (see the kernel for what com, gcom and grad_out are with LOSS)
+static void launch_crop_bwd_tiled(hipStream_t stream, const float* dims, const float* com, const float* gcom, const float* grad_out,
+                                  int64_t B, int64_t Hh, int64_t W, double crop_width, double crop_height, float* grad_flux,
+                                  const float* grad_loss = nullptr, int64_t grad_loss_stride = 1)
+{
+    hipLaunchKernelGGL(flux_crop_bwd_tiled_kernel<LOSS>,
+                       dim3((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((Hh + kTileY - 1) / kTileY), (unsigned)B),
+                       dim3(256), 0, stream, dims, com, gcom, grad_out, (int)Hh, (int)W, (float)crop_width, (float)crop_height,
+                       grad_flux, grad_loss, (int)grad_loss_stride);
+}
+
 static bool crop_args_ok(const void* a, const void* b, const void* c, const void* d, int64_t B, int64_t Hh, int64_t W)
 {
     return a && b && c && d && B >= 0 && Hh >= 1 && W >= 1 && Hh <= 65535 && Hh * W <= (int64_t)1 << 30 && B <= 65535;
@@ -965,7 +822,7 @@ extern "C" int art_flux_crop_fwd(const float* flux, const float* target_dims, in
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, out, centers, B, Hh, W)) return ART_EINVAL;
-    hipLaunchKernelGGL(flux_com_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, centers);
+    hipLaunchKernelGGL(flux_com_kernel<NormalisedWeights>, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, centers);
     hipLaunchKernelGGL(flux_crop_fwd_kernel,
                        dim3((unsigned)((W + kFluxBlock - 1) / kFluxBlock), (unsigned)((Hh + kCropRows - 1) / kCropRows), (unsigned)B),
                        dim3(kFluxBlock), 0, stream, flux, target_dims, centers, (int)Hh, (int)W, (float)crop_width,
@@ -983,10 +840,7 @@ extern "C" int art_flux_crop_bwd(const float* flux, const float* target_dims, co
     if (!crop_args_ok(flux, target_dims, centers, grad_out, B, Hh, W) || !grad_flux || !workspace) return ART_EINVAL;
     hipLaunchKernelGGL(flux_crop_bwd_com_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, target_dims, centers,
                        grad_out, (int)Hh, (int)W, (float)crop_width, (float)crop_height, workspace);
-    hipLaunchKernelGGL(flux_crop_bwd_tiled_kernel<false>,
-                       dim3((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((Hh + kTileY - 1) / kTileY), (unsigned)B),
-                       dim3(256), 0, stream, target_dims, centers, workspace, grad_out, (int)Hh, (int)W,
-                       (float)crop_width, (float)crop_height, grad_flux, (const float*)nullptr);
+    launch_crop_bwd_tiled<false>(stream, target_dims, centers, workspace, grad_out, B, Hh, W, crop_width, crop_height, grad_flux);
     ART_HIP(hipGetLastError());
     return ART_OK;
 }
@@ -1053,10 +907,8 @@ extern "C" int art_flux_crop_pixel_loss_bwd(const float* target_dims, const floa
     if (!crop_args_ok(residual, target_dims, center_grad_unit, centers4, B, Hh, W) || !grad_loss || !grad_flux ||
         (grad_loss_stride != 0 && grad_loss_stride != 1))
         return ART_EINVAL;
-    hipLaunchKernelGGL(flux_crop_bwd_tiled_kernel<true>,
-                       dim3((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((Hh + kTileY - 1) / kTileY), (unsigned)B),
-                       dim3(256), 0, stream, target_dims, centers4, center_grad_unit, residual, (int)Hh, (int)W, (float)crop_width,
-                       (float)crop_height, grad_flux, grad_loss, (int)grad_loss_stride);
+    launch_crop_bwd_tiled<true>(stream, target_dims, centers4, center_grad_unit, residual, B, Hh, W, crop_width, crop_height, grad_flux,
+                                grad_loss, grad_loss_stride);
     ART_HIP(hipGetLastError());
     return ART_OK;
 }
@@ -1066,7 +918,7 @@ extern "C" int art_flux_center_of_mass(const float* flux, int64_t B, int64_t Hh,
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, com, flux, com, B, Hh, W)) return ART_EINVAL;
-    hipLaunchKernelGGL(flux_com_px_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, com);
+    hipLaunchKernelGGL(flux_com_kernel<PixelWeights>, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, com);
     ART_HIP(hipGetLastError());
     return ART_OK;
 }
@@ -1110,10 +962,7 @@ extern "C" int art_flux_crop_kl_loss_bwd(const float* flux, const float* target_
     hipLaunchKernelGGL(flux_crop_kl_loss_bwd_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, target_dims,
                        ground_truth, record8, grad_loss, (int)Hh, (int)W, (float)crop_width, (float)crop_height, grad_crop, com3,
                        gcom);
-    hipLaunchKernelGGL(flux_crop_bwd_tiled_kernel<false>,
-                       dim3((unsigned)((W + kTileX - 1) / kTileX), (unsigned)((Hh + kTileY - 1) / kTileY), (unsigned)B),
-                       dim3(256), 0, stream, target_dims, com3, gcom, grad_crop, (int)Hh, (int)W, (float)crop_width,
-                       (float)crop_height, grad_flux, (const float*)nullptr);
+    launch_crop_bwd_tiled<false>(stream, target_dims, com3, gcom, grad_crop, B, Hh, W, crop_width, crop_height, grad_flux);
     ART_HIP(hipGetLastError());
     return ART_OK;
 }

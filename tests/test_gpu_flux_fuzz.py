@@ -174,6 +174,27 @@ def test_fused_crop_kl_loss_vs_fp64_chain(case):
     assert not bad, bad
 
 
+# the centre-of-mass loops and the two shapes at which the scalar loop runs in more than one trip (33 x 65 and 33 x 17 pixels on
+# 1024 threads): the scalar loop, the float4 loop with W / 4 above and below the block size, and the remainder case
+ONE_ROUTINE = flux_ref.CENTRE_LOOPS + [c for c in flux_ref.CASES if (c.B, c.Hh, c.W) in ((3, 33, 65), (2, 33, 17))]
+
+
+@pytest.mark.parametrize("case", ONE_ROUTINE, ids=[flux_ref.case_id(c) for c in ONE_ROUTINE])
+def test_crop_and_fused_kl_form_the_same_centre_bits(case):
+    """The unfused crop and the fused crop + KL loss form a bitmap's centre of mass with one routine: ``centers`` of
+    ``art_flux_crop_fwd`` and the first three floats of each ``record8`` row of ``art_flux_crop_kl_loss_fwd`` are the same bits."""
+    from artist_amd import _lib
+    assert len(ONE_ROUTINE) == 5
+    d = inputs(case)
+    B, Hh, W = d["flux"].shape
+    crop, centers = torch.empty_like(d["flux"]), torch.empty((B, 3), device=DEV)
+    loss, record8 = torch.empty(B, device=DEV), torch.empty((B, 8), device=DEV)
+    p = lambda x: x.data_ptr()
+    _lib.call("art_flux_crop_fwd", DEV, p(d["flux"]), p(d["dims"]), B, Hh, W, CROP_W, CROP_H, p(crop), p(centers))
+    _lib.call("art_flux_crop_kl_loss_fwd", DEV, p(d["flux"]), p(d["dims"]), p(d["truth"]), B, Hh, W, CROP_W, CROP_H, p(loss), p(record8))
+    np.testing.assert_array_equal(n(centers).view(np.uint32), np.ascontiguousarray(n(record8)[:, :3]).view(np.uint32))
+
+
 def test_empty_batch_returns_cleanly():
     """B = 0 (a rank without an active heliostat): every entry point returns ART_OK without a launch, given valid pointers or
     the null pointers of empty tensors; the Python classes return empty results and empty gradients."""

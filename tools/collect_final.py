@@ -9,7 +9,7 @@ names = {"final_bench.json": "bench_line.json", "final_bench_h125.json": "bench_
          "final_config_bench.jsonl": "config_bench.jsonl", "final_bench_2rank_gloo.log": "bench_2rank_gloo.log",
          "final_bench_rccl_world1.log": "bench_rccl_world1.log", "final_blocking_bench.json": "blocking_bench.json",
          "final_cylinder_bench.json": "cylinder_bench.json", "final_flux_bench_1000.json": "flux_bench.json",
-         "final_flux_bench_125.json": "flux_bench_125.json", "final_flux_ab_r03.txt": "flux_ab_vs_r03.txt",
+         "final_flux_bench_125.json": "flux_bench_125.json",
          "final_nurbs_bench.json": "nurbs_bench.json", "final_nurbs_mfma_bench.json": "nurbs_mfma_bench.json",
          "final_pipeline_probe.txt": "pipeline_probe.txt", "final_kstats.txt": "kernel_stats_top.txt",
          "final_kstats_h125.txt": "kernel_stats_top_h125.txt", "final_gap_h125.txt": "gap_report_h125.txt", "final_gap.txt": "gap_report.txt",

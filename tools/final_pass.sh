@@ -19,7 +19,6 @@ timeout -k 10 200 python tools/adam_bench.py 2>/dev/null | tail -1 > $OUT/final_
 timeout -k 10 200 python tools/per_target_bench.py 2>/dev/null | tail -1 > $OUT/final_per_target_bench.json
 timeout -k 10 200 python tools/parity_margins.py 2>/dev/null | grep "hip-oracle" > $OUT/final_parity_margins.txt
 for B in 1000 125; do timeout -k 10 300 python tools/flux_bench.py $B 2>/dev/null | tail -1 > $OUT/final_flux_bench_$B.json; done
-timeout -k 10 300 python tools/flux_ab_r03.py 1000 > $OUT/final_flux_ab_r03.txt 2>/dev/null; timeout -k 10 300 python tools/flux_ab_r03.py 125 >> $OUT/final_flux_ab_r03.txt 2>/dev/null
 timeout -k 10 300 python tools/cylinder_bench.py 2>/dev/null | tail -1 > $OUT/final_cylinder_bench.json
 timeout -k 10 300 python tools/nurbs_bench.py 1000 125 2>/dev/null | tail -1 > $OUT/final_nurbs_bench.json
 timeout -k 10 120 ./tools/bin/nurbs_mfma_bench > $OUT/final_nurbs_mfma_bench.json 2>&1
