@@ -127,6 +127,12 @@ _BY_MODULE_HEADER = {
         "art_cant_facets_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
         "art_cant_facets_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
     },
+    "modules/artist_hip_shading.h": {
+        "art_shading_cull": (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_i64, _c_dbl, _c_i64, _ptr, _ptr, _ptr]),
+        "art_shading_prims_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr]),
+        "art_shading_prims_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
+        "art_shading_append": (_c_int, [_ptr, _ptr, _c_i64, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
+    },
 }
 
 MODULE_SIGNATURES = {name: signature for table in _BY_MODULE_HEADER.values() for name, signature in table.items()}

@@ -11,12 +11,18 @@ because its mask is a dense ``[rays x primitives]`` tensor; a leaf of that tree 
 ray passes the leaf's own box test, so the set it returns is the set of primitives whose box is hit by at
 least one foreign ray.  The HIP path computes that same set directly (per-heliostat beam cull + per-ray box
 test, ``art_blocking_filter``), no tree needed.
+
+Shading - the sun ray to a mirror point stopped by a neighbour - is blocking by per-heliostat sheared copies of the
+rectangles (``create_shading_primitives``): which neighbours can shade whom and the sheared tables with
+their adjoint are HIP kernels (``artist_amd/csrc/shading_kernels.hip``), the per-ray work is the trace kernels' as it is.
 """
 from __future__ import annotations
 
 import math
 
 import torch
+
+from . import _lib, ops
 
 
 def _spans_and_normals(corners: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -67,3 +73,79 @@ def create_blocking_primitives_rectangle(blocking_heliostats_surface_points: tor
     corners = torch.gather(aligned, 1, index[:, :, None].expand(-1, -1, 4))
     spans, normals = _spans_and_normals(corners)
     return corners, spans, normals
+
+
+class ShadingTables(torch.autograd.Function):
+    """The sheared tables ``(corners [H*S,4,4], spans [H*S,2,4], normals [H*S,4])`` of the rectangles listed in ``shader_idx``
+    ``[H,S]`` (``art_shading_prims_fwd`` / ``_bwd``, include/modules/artist_hip_shading.h), differentiable w.r.t.
+    ``prim_corners`` through the shader's corners and through the shaded heliostat's own plane; ``incident`` is a constant."""
+
+    @staticmethod
+    def forward(ctx, prim_corners, owner, incident, shader_idx):
+        dev = ops._require_cuda(prim_corners, owner, incident, shader_idx)
+        corners, incident = ops._f32c(prim_corners), ops._f32c(incident)
+        H, S = int(shader_idx.shape[0]), int(shader_idx.shape[1])
+        N = int(corners.shape[0])
+        if corners.shape != (N, 4, 4) or incident.shape != (H, 4) or owner.shape != (H,):
+            raise ValueError("prim_corners must be [N,4,4], incident [H,4], owner [H] and shader_idx [H,S]")
+        if owner.dtype != torch.int32 or shader_idx.dtype != torch.int32 or not (owner.is_contiguous() and shader_idx.is_contiguous()):
+            raise ValueError("owner and shader_idx must be contiguous int32 tensors")
+        out_c = torch.empty((H * S, 4, 4), dtype=torch.float32, device=dev)
+        out_s = torch.empty((H * S, 2, 4), dtype=torch.float32, device=dev)
+        out_n = torch.empty((H * S, 4), dtype=torch.float32, device=dev)
+        _lib.call("art_shading_prims_fwd", dev, corners.data_ptr(), owner.data_ptr(), incident.data_ptr(), shader_idx.data_ptr(),
+                  H, N, S, out_c.data_ptr(), out_s.data_ptr(), out_n.data_ptr())
+        ctx.save_for_backward(corners, owner, incident, shader_idx)
+        ctx.set_materialize_grads(False)
+        return out_c, out_s, out_n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_c, g_s, g_n):
+        corners, owner, incident, shader_idx = ctx.saved_tensors
+        if (g_c is None and g_s is None and g_n is None) or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        dev = corners.device
+        H, S = int(shader_idx.shape[0]), int(shader_idx.shape[1])
+        N = int(corners.shape[0])
+        g_c = torch.zeros((H * S, 4, 4), dtype=torch.float32, device=dev) if g_c is None else ops._f32c(g_c)
+        g_s = torch.zeros((H * S, 2, 4), dtype=torch.float32, device=dev) if g_s is None else ops._f32c(g_s)
+        g_n = torch.zeros((H * S, 4), dtype=torch.float32, device=dev) if g_n is None else ops._f32c(g_n)
+        scratch = torch.empty((H * S * 24,), dtype=torch.float32, device=dev)
+        grad = torch.empty_like(corners)
+        _lib.call("art_shading_prims_bwd", dev, corners.data_ptr(), owner.data_ptr(), incident.data_ptr(), shader_idx.data_ptr(),
+                  g_c.data_ptr(), g_s.data_ptr(), g_n.data_ptr(), H, N, S, scratch.data_ptr(), grad.data_ptr())
+        return grad, None, None, None
+
+
+def shading_cull(prim_corners: torch.Tensor, owner: torch.Tensor, incident: torch.Tensor, max_scatter_angle: float,
+                 slots: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(shader_idx [H,S] int32, shade_count [H] int32)``: per traced heliostat the rectangles that can shade it, ascending,
+    ``-1`` in the empty slots, and the number found, which may exceed ``S`` (``art_shading_cull``: the rule is stated in
+    artist_amd/csrc/shading_kernels.hip).  No gradient, nothing read back.  ``slots`` = None: ``ops.SHADING_SLOTS``."""
+    dev = ops._require_cuda(prim_corners, owner, incident)
+    S = int(ops.SHADING_SLOTS if slots is None else slots)
+    corners, incident = ops._f32c(prim_corners.detach()), ops._f32c(incident.detach())
+    H, N = int(incident.shape[0]), int(corners.shape[0])
+    if corners.shape != (N, 4, 4) or incident.shape != (H, 4) or owner.shape != (H,):
+        raise ValueError("prim_corners must be [N,4,4], incident [H,4] and owner [H]")
+    if not max_scatter_angle >= 0.0:
+        raise ValueError("max_scatter_angle must be the largest |distortion angle| of the trace (>= 0)")
+    owner = ops._int32c(owner)
+    shader_idx = torch.empty((H, S), dtype=torch.int32, device=dev)
+    shade_count = torch.empty((H,), dtype=torch.int32, device=dev)
+    _lib.call("art_shading_cull", dev, corners.data_ptr(), owner.data_ptr(), incident.data_ptr(), H, N, float(max_scatter_angle), S,
+              shader_idx.data_ptr(), shade_count.data_ptr())
+    return shader_idx, shade_count
+
+
+def create_shading_primitives(prim_corners: torch.Tensor, owner: torch.Tensor, incident: torch.Tensor, max_scatter_angle: float,
+                              slots: int | None = None) -> dict:
+    """The shading tables of a trace: for each traced heliostat ``h`` (own rectangle ``owner[h]``, sun rays along
+    ``incident[h]``) the rectangles that can shade it, sheared by ``A_h`` so that blocking of the REFLECTED ray by the sheared
+    copy is shading of the sunward ray by the rectangle.  Returns ``corners [H*S,4,4]``, ``spans [H*S,2,4]``,
+    ``normals [H*S,4]`` (in the autograd graph of ``prim_corners``), ``shader_idx [H,S]`` and ``shade_count [H]``; row
+    ``h*S + k`` belongs to heliostat ``h`` alone."""
+    shader_idx, shade_count = shading_cull(prim_corners, owner, incident, max_scatter_angle, slots)
+    corners, spans, normals = ShadingTables.apply(prim_corners, ops._int32c(owner), incident.detach(), shader_idx)
+    return dict(corners=corners, spans=spans, normals=normals, shader_idx=shader_idx, shade_count=shade_count)

@@ -23,7 +23,7 @@ import weakref
 import torch
 
 from . import ops
-from .blocking import create_blocking_primitives_rectangles_by_index
+from .blocking import create_blocking_primitives_rectangles_by_index, create_shading_primitives
 from .sampling import DistortionsDataset, RestrictedDistributedSampler
 
 log = logging.getLogger(__name__)
@@ -91,17 +91,24 @@ def _cylinder_tables(tower):
 
 
 class HeliostatRayTracer:
-    """See ``artist/raytracing/heliostat_ray_tracer.py:19-69`` for the attribute documentation."""
+    """See ``artist/raytracing/heliostat_ray_tracer.py:19-69`` for the attribute documentation.
+
+    ``shading_active`` (an extension; the reference has no shading): the sun ray to a mirror point can be stopped by a
+    neighbouring heliostat before it arrives, evaluated with the blocking mask against per-heliostat sheared copies of the
+    neighbours' rectangles.  The third factor returned by ``trace_rays``, ``blocking_factor``, then counts the
+    rays that are neither blocked nor shaded.  ``shading_active=True`` with ``blocking_active=False`` traces with shading
+    only: the rectangles are built, the blocking filter is skipped."""
 
     #: publish ``heliostat_group.preferred_reflection_directions`` like the reference does (:285-290)
     publish_reflection_directions = True
 
     def __init__(self, scenario, heliostat_group, blocking_active: bool = True, world_size: int = 1, rank: int = 0,
                  batch_size: int = 100, random_seed: int = 7, bitmap_resolution: torch.Tensor = _DEFAULT_RESOLUTION,
-                 dni: float | None = None) -> None:
+                 dni: float | None = None, shading_active: bool = False) -> None:
         self.scenario = scenario
         self.heliostat_group = heliostat_group
         self.blocking_active = blocking_active
+        self.shading_active = shading_active
         self.world_size = world_size
         self.rank = rank
         self.batch_size = batch_size   # accepted for API parity; the fused kernel has no per-ray intermediates
@@ -126,7 +133,7 @@ class HeliostatRayTracer:
         self.bitmap_resolution = bitmap_resolution
         self._resolution_host = (int(bitmap_resolution[0]), int(bitmap_resolution[1]))
 
-        if self.blocking_active:
+        if self.blocking_active or self.shading_active:
             # heliostat_ray_tracer.py:159-183: every heliostat of every group can block; aligned surfaces where a
             # group has been aligned, horizontal ones at their positions otherwise
             surfaces = []
@@ -150,6 +157,8 @@ class HeliostatRayTracer:
         #: indices of the rectangles the last ``trace_rays`` call filtered (blocking only)
         self._filter_flags = self._filtered = None
         self._owner_cache = None
+        #: ``(shader_idx [H,S], shade_count [H])`` of the last ``trace_rays`` call (shading only), on the device
+        self._shading = None
 
         if dni is not None:
             # heliostat_ray_tracer.py:185-201
@@ -213,11 +222,19 @@ class HeliostatRayTracer:
             target_area_indices = target_area_indices.index_select(0, idx)
 
         width, height = self._resolution_host
+        rectangles = self._blocking_arguments(idx, active_heliostats_mask)
+        shading = ()
+        if self.shading_active:
+            corners, _, _, owner, max_scatter, _ = rectangles
+            tabs = create_shading_primitives(corners, owner, incident_ray_directions, max_scatter)
+            self._shading = (tabs["shader_idx"], tabs["shade_count"])     # (diagnostics: the last call's lists, on the device)
+            shading = (tabs["corners"], tabs["spans"], tabs["normals"], tabs["shader_idx"], tabs["shade_count"],
+                       bool(self.blocking_active))
         flux, factors, flags = ops.TraceRays.apply(
             points, normals, incident_ray_directions, dist_u, dist_e, target_area_indices, *_planar_tables(tower, points.device),
             float(self.ray_magnitude), float(ray_extinction_factor), float(mirror_reflectivity), width, height, bool(per_target),
-            _cylinder_tables(tower), *(self._blocking_arguments(idx, active_heliostats_mask) or (None, None, None, None, -1.0, True)),
-            self._points_per_facet(points))
+            _cylinder_tables(tower), *(rectangles or (None, None, None, None, -1.0, True)),
+            self._points_per_facet(points), *shading)
         if self.blocking_active:
             self._filter_flags, self._filtered = flags, None       # (indices on demand: nonzero() waits for the device)
         return flux, factors[0], factors[1], factors[2]
@@ -227,7 +244,8 @@ class HeliostatRayTracer:
                    mirror_reflectivity: float = 0.935, device: torch.device | None = None
                    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """Heliostat ray tracing (:220-508).  Returns ``(flux [H,res_u,res_e], intercept_factor [H],
-        on_target_factor [H], blocking_factor [H])`` for the heliostat samples owned by this rank."""
+        on_target_factor [H], blocking_factor [H])`` for the heliostat samples owned by this rank.  With ``shading_active``
+        the blocking factor is the fraction of rays that are neither blocked nor shaded."""
         return self._trace(incident_ray_directions, active_heliostats_mask, target_area_indices, ray_extinction_factor,
                            mirror_reflectivity, device, per_target=False)
 
@@ -279,7 +297,7 @@ class HeliostatRayTracer:
 
     def _blocking_arguments(self, idx, active_heliostats_mask):
         """Rectangles of all heliostats (:291-301) + the rectangle index of each traced heliostat (:445-448)."""
-        if not self.blocking_active:
+        if not (self.blocking_active or self.shading_active):
             return ()
         corners, spans, normals = create_blocking_primitives_rectangles_by_index(self.blocking_heliostat_surfaces_active)
         # rectangle index of each active heliostat: once per mask tensor object and version (nonzero() waits for the device)
