@@ -8,6 +8,7 @@
 
 #include "ray_math.hpp"
 #include "launch_common.hpp"
+#include "trace_diag.hpp"
 
 namespace art {
 
@@ -103,6 +104,10 @@ template <bool INTERLEAVED>
 __device__ __forceinline__ void load_dist_row(const float* __restrict__ row_u, const float* __restrict__ row_e,
                                               int lane_off, float& u, float& e)
 {
+    if (diag::kNoLoads) {     // ablation: angles synthesised in registers, no HBM stream
+        u = 1e-6f * (float)(lane_off & 1023); e = -1e-6f * (float)((lane_off >> 3) & 1023);
+        return;
+    }
     if constexpr (INTERLEAVED) {
         const float2 v = *reinterpret_cast<const float2*>(row_u + lane_off);
         u = v.x; e = v.y;
@@ -117,6 +122,10 @@ template <bool INTERLEAVED>
 __device__ __forceinline__ void load_dist_stream(const float* __restrict__ row_u, const float* __restrict__ row_e,
                                                  int lane_off, float& u, float& e)
 {
+    if (diag::kNoLoads) {
+        u = 1e-6f * (float)(lane_off & 1023); e = -1e-6f * (float)((lane_off >> 3) & 1023);
+        return;
+    }
     typedef float v2f __attribute__((ext_vector_type(2)));
     // scalar base + zero-extended 32-bit byte offset: the form `global_load ... v_off, s[base:base+1]` takes without any
     // 64-bit vector arithmetic (lane_off >= 0: an element offset inside one heliostat's row)

@@ -23,6 +23,7 @@
 
 #include <type_traits>
 
+#define ART_TIMELINE_RECORDS_HERE      // trace_diag.hpp: the timeline's device array and hooks belong to this translation unit
 #include "trace_common.hpp"
 #include "flux_moments.hpp"
 
@@ -754,6 +755,8 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
     const int64_t dbase = (int64_t)h * a.sh + (int64_t)r0 * a.sr;
 
     // ---- phase 1: window ---------------------------------------------------------------------
+    diag::Timeline tl;
+    tl.begin(bid);
     if (tid < 3) s_cnt[tid] = 0;
     // This thread's first point and its first distortion sample are requested before anything else, and the tile is
     // cleared while they are in flight: a CU holds ONE workgroup (the window fills its LDS), so every microsecond of
@@ -772,6 +775,7 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
     const int n_prims = load_prims<BLOCKING, false>(a, h, s_tab);
     compute_window<INTERLEAVED, CYL>(a, pl, cy, inc, org, nrm, p0, p1, dbase, s_red, &s_win, &fp);
     const Window win = s_win;
+    tl.mark(2);
     // (an empty window - no chief ray reaches the target - must hold no ray: bounds of 0, not of (unsigned)-1)
     const unsigned twm1 = (unsigned)max(win.tw - 1, 0), uthm1 = (unsigned)max(win.th - 1, 0);
     const int dummy = a.tile_cap;                    // two spare cells: [tile_cap], [tile_cap + 1]
@@ -794,6 +798,7 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
         for (int i = tid; i < npx; i += blockDim.x) tile[i] = 0u;
         __syncthreads();
     }
+    tl.mark(3);
 
     // ---- phase 2: trace ----------------------------------------------------------------------
     // Every ray issues its four LDS adds unconditionally: rays that are off the bitmap or outside the
@@ -887,16 +892,22 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
             ps.q1 = cvt_nearest_u32(cle * chu * Is); ps.q2 = cvt_nearest_u32(che * chu * Is);
             ps.q3 = cvt_nearest_u32(che * clu * Is); ps.q4 = cvt_nearest_u32(cle * clu * Is);
             ps.ie = ie; ps.iu = iu;
-            ps.o1 = atomicAdd(tile + cell_hi, ps.q1);
-            ps.o2 = atomicAdd(tile + cell_hi + 1, ps.q2);
-            ps.o3 = atomicAdd(tile + cell_lo + 1, ps.q3);
-            ps.o4 = atomicAdd(tile + cell_lo, ps.q4);
+            if (diag::kNoLdsAtomics) {     // ablation: the operands stay alive, the LDS traffic goes
+                asm volatile("" ::"v"(cell_hi), "v"(cell_lo), "v"(ps.q1), "v"(ps.q2), "v"(ps.q3), "v"(ps.q4));
+            } else {
+                ps.o1 = atomicAdd(tile + cell_hi, ps.q1);
+                ps.o2 = atomicAdd(tile + cell_hi + 1, ps.q2);
+                ps.o3 = atomicAdd(tile + cell_lo + 1, ps.q3);
+                ps.o4 = atomicAdd(tile + cell_lo, ps.q4);
+            }
             if (__builtin_expect((m_valid & ~m_inwin) != 0ull, 0)) {
                 // valid but not in this pass's band: another band's ray, the last pixel row/column
                 // (heliostat_ray_tracer.py:723-728), or a stray of the union window -> global atomics, once
                 const bool on = (tbe + 1.0f < Wf) && (tbu + 1.0f < Hf);
                 const bool in_union = (unsigned)le < twm1 && (unsigned)(iu - win.u0) < uthm1;
-                if (first && valid && on && !in_union) {
+                // (if constexpr: a discarded statement of this generic lambda names - and captures - nothing)
+                if constexpr (diag::kCountStrays) { if (first) n_free += __popcll(__builtin_amdgcn_ballot_w64(valid && on && !in_union)); }
+                if (!diag::kNoStrays && first && valid && on && !in_union) {
                     unsigned long long* row_hi = acc + (int64_t)(a.Hh - 2 - iu) * a.W + ie;
                     unsigned long long* row_lo = row_hi + a.W;
                     const float Iss = fabsf(I) * win.scale;              // as for a window ray
@@ -919,6 +930,7 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
         load_dist_row<INTERLEAVED>(bu_ + (int64_t)min(2, nr - 1) * a.sr, be_ + (int64_t)min(2, nr - 1) * a.sr, lane_off, cu2, ce2);
         load_dist_row<INTERLEAVED>(bu_ + (int64_t)min(3, nr - 1) * a.sr, be_ + (int64_t)min(3, nr - 1) * a.sr, lane_off, cu3, ce3);
         for (int k = 0; k < nr; k += 4) {
+            tl.mark_landed(k == 4 && p == p0 && tid == 0, 4);      // the first group is traced
             float nu0, ne0, nu1, ne1, nu2, ne2, nu3, ne3;
             const int64_t o4 = (int64_t)min(k + 4, nr - 1) * a.sr, o5 = (int64_t)min(k + 5, nr - 1) * a.sr;
             const int64_t o6 = (int64_t)min(k + 6, nr - 1) * a.sr, o7 = (int64_t)min(k + 7, nr - 1) * a.sr;
@@ -947,9 +959,10 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
     resolve_carries(ps, acc, a.W, a.Hh, win.shift);
     if (first && lane == 0) {                                                           // wave totals
         atomicAdd(&s_cnt[0], lean ? n_valid : n_int); atomicAdd(&s_cnt[1], n_valid);
-        if constexpr (BLOCKING) atomicAdd(&s_cnt[2], n_free);
+        if constexpr (BLOCKING || diag::kCountStrays) atomicAdd(&s_cnt[2], n_free);
     }
     __syncthreads();
+    tl.mark(5);
     // the next work item is requested now and published after the flush: the counter's round trip hides behind it
     unsigned next_item = 0u;
     if (tid == 0 && pass == win.npass - 1) next_item = fetch_work_item(work_counter, a);
@@ -960,11 +973,14 @@ __device__ __forceinline__ void trace_fwd_item(const TraceArgs& a, float* __rest
         const unsigned* trow = tile + row * win.tw;
         for (int c = lane; c < win.tw; c += 64) {
             const unsigned q = trow[c];
-            if (q != 0u) atomicAdd(g + c, (unsigned long long)q << win.shift);
+            // (ablation: the loop stays, its global atomics go)
+            if (diag::kNoFlush ? q == 0xFFFFFFFFu : q != 0u) atomicAdd(g + c, (unsigned long long)q << win.shift);
         }
     }
     if (tid == 0 && pass == win.npass - 1) *s_next = (int)(gridDim.x + next_item);
     __syncthreads();   // the band is flushed before the next pass re-zeroes the tile
+    tl.mark(6);
+    tl.span(7);
   }
     if (tid < 3 && s_cnt[tid]) atomicAdd(&counts[tid * a.H + h], s_cnt[tid]);
 }
@@ -1130,6 +1146,8 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
 
     // ---- phase 1: window (as in the generic item) - or, when the launch came with its windows (window_table_kernel), only the
     //      clearing of the tile -----------------------------------------------------------------------------------------------
+    diag::Timeline tl;
+    tl.begin(bid);
     if (tid < 3) s_cnt[tid] = 0;
     const Window* const win_table = static_cast<const Window*>(a.win_table);
     const int pf = (a.win_sample != 0 && p1 - p0 > (int)blockDim.x) ? window_sample_point(p0, p1) : p0 + tid;
@@ -1148,6 +1166,8 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
     if (win_table != nullptr) __syncthreads();
     else compute_window<INTERLEAVED, CYL>(a, pl, cy, inc, org, nrm, p0, p1, dbase, s_red, &s_win, &fp);
     const Window win = s_win;
+    tl.mark(2);
+    tl.window(win.npass, win.tw, win.th);
     const float Wf = (float)a.W, Hf = (float)a.Hh;
     // (Packing the edge points into the block's last waves, which takes 8 % off the backward kernel, was measured here too:
     //  3.25 -> 3.32 ... 3.43 ms for margins of 1/4 ... 3/4 of the scatter pad - a stray costs this kernel its atomics, which
@@ -1313,21 +1333,26 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
             ptbe = tbe; ptbu = tbu;
             lds_u32* up = (lds_u32*)(size_t)addr_up;
             lds_u32* lo = (lds_u32*)(size_t)addr_lo;
-            po1 = __hip_atomic_fetch_add(up, pq1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            po2 = __hip_atomic_fetch_add(up + 1, pq2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            po3 = __hip_atomic_fetch_add(lo + 1, pq3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            po4 = __hip_atomic_fetch_add(lo, pq4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (diag::kNoLdsAtomics) {     // ablation: the operands stay alive, the LDS traffic goes
+                asm volatile("" ::"v"(up), "v"(lo), "v"(pq1), "v"(pq2), "v"(pq3), "v"(pq4));
+            } else {
+                po1 = __hip_atomic_fetch_add(up, pq1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                po2 = __hip_atomic_fetch_add(up + 1, pq2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                po3 = __hip_atomic_fetch_add(lo + 1, pq3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                po4 = __hip_atomic_fetch_add(lo, pq4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
             // Valid rays outside this pass's window: strays of the union window (or, when the footprint is swept in
             // bands, rays of another band; or rays on the last pixel row / column, heliostat_ray_tracer.py:723-728).
             // A stray lane PARKS its ray - pixel coordinates and direction cosine, three registers - and the wave moves
             // on: one stray lane used to drag its whole wave through ~50 instructions of address arithmetic and four
             // atomics in 45 % of the ray steps.  The parked rays go to their pixels' accumulators when a lane that is
             // already holding one strays again (every ~10 strays of a wave) and at the end of the item.
-            unsigned long long m_out = m_valid & ~m_in;
+            unsigned long long m_out = diag::kNoStrays ? 0ull : m_valid & ~m_in;      // (ablation: no ray strays)
             if (__builtin_expect(m_out != 0ull, 0)) {
                 if (!first) m_out = 0ull;
                 else if (win.npass > 1)                         // banded sweep: only what no band holds
                     m_out &= ~(win_ok & ballot64(f32_bits(lef) <= twm2_bits) & ballot64(f32_bits(tbu - u0f) <= uthm2_bits));
+                diag::Timeline::count_strays(m_out, m_parked);
                 if (m_out & m_parked) unpark();
                 pk_be = select_mask(m_out, be, pk_be); pk_bu = select_mask(m_out, bu, pk_bu); pk_ah = select_mask(m_out, ahk, pk_ah);
                 m_parked |= m_out;
@@ -1385,6 +1410,7 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
     __syncthreads();
     unsigned next_item = 0u;
     if (tid == 0 && pass == win.npass - 1) next_item = fetch_work_item(work_counter, a);
+    if (first) tl.mark(7);      // (lean items: slot 7 = start of the first flush)
 
     // ---- phase 3: flush ------------------------------------------------------------------------
     for (int row = wave; row < pth; row += nwaves) {
@@ -1392,12 +1418,14 @@ __device__ __forceinline__ void trace_fwd_item_lean(const TraceArgs& a, float* _
         const unsigned* trow = tile + row * win.tw;
         for (int c = lane; c < win.tw; c += 64) {
             const unsigned q = trow[c];
-            if (q != 0u) atomicAdd(g + c, (unsigned long long)q << win.shift);
+            if (diag::kNoFlush ? q == 0xFFFFFFFFu : q != 0u) atomicAdd(g + c, (unsigned long long)q << win.shift);
         }
     }
     if (tid == 0 && pass == win.npass - 1) *s_next = (int)(gridDim.x + next_item);
     __syncthreads();
   }
+    tl.mark(6);                 // (the flush is not stamped apart from the trace here)
+    tl.end_lean(3, 5);          // slot 3: un-park events | stray rays, slot 5: shader clocks of the item
     if (tid < (BLOCKING ? 3 : 2) && s_cnt[tid]) atomicAdd(&counts[tid * a.H + h], s_cnt[tid]);
 }
 
@@ -1429,6 +1457,8 @@ __device__ __forceinline__ void trace_fwd_item_field(const TraceArgs& a, unsigne
     const Cyl cy = {};
     unsigned next_item = 0u;
     bool fetched = false;
+    diag::Timeline tl;          // (a group of heliostats: its start and its end are stamped, not the phases of its runs)
+    tl.begin(group);
     for (int hs = g0; hs < g1;) {
         const int t = a.target_idx[hs];
         // workgroup-uniform: a bad index (reported), a cylinder's or a blocked heliostat (another launch's)
@@ -1586,6 +1616,8 @@ __device__ __forceinline__ void trace_fwd_item_field(const TraceArgs& a, unsigne
         __syncthreads();                 // flushed before the next run clears the tile
         hs = he;
     }
+    tl.mark(6);
+    tl.span(7);
     if (tid == 0) {
         if (!fetched) next_item = fetch_work_item(work_counter, a);     // (the group ended with skipped heliostats)
         *s_next = (int)(gridDim.x + next_item);
@@ -1711,6 +1743,7 @@ __global__ void finalize_factors_kernel(float* factors, int H, float rays_per_he
     factors[h] = (float)n_int / rays_per_heliostat;
     factors[H + h] = (float)n_on / rays_per_heliostat;
     // blocking off: blocked == 0 everywhere
+    if (diag::kCountStrays) blocking = 1;
     // (split launches: a heliostat with an empty candidate list went through the lean kernel, which does not count free rays)
     if (unblocked_if_empty != nullptr && unblocked_if_empty[h] == 0) blocking = 0;
     factors[2 * H + h] = (blocking ? (float)n_free : rays_per_heliostat) / rays_per_heliostat;
@@ -2026,6 +2059,12 @@ __device__ __forceinline__ void stage_grad_window(const float* __restrict__ g, i
 
 // (The cylinder and blocking instantiations keep ~60 more live values per ray; they run 768-thread workgroups =
 // 168 VGPRs, see kCylBwdThreads.)
+// a backward item's record in the diagnostic timeline (diag::Timeline): heliostat, point block, sample chunk
+__device__ __forceinline__ int bwd_timeline_slot(const TraceArgs& a, const WorkItem& item)
+{
+    return item.h * a.n_pblocks * a.n_rchunks + item.pblock * a.n_rchunks + item.r0 / max(a.r_chunk, 1);
+}
+
 template <bool INTERLEAVED, bool ATOMIC_OUT, bool CYL, bool BLOCKING>
 __device__ __forceinline__ void trace_bwd_item(const TraceArgs& a, const float* __restrict__ grad_flux,
                                                float4* __restrict__ grad_origins, float4* __restrict__ grad_normals,
@@ -2076,9 +2115,12 @@ __device__ __forceinline__ void trace_bwd_item(const TraceArgs& a, const float* 
     const float4* __restrict__ nrm = a.normals + (int64_t)h * a.P;
     const int64_t dbase = (int64_t)h * a.sh + (int64_t)r0 * a.sr;
 
+    diag::Timeline tl;
+    tl.begin(bwd_timeline_slot(a, item));
     const int n_prims = load_prims<BLOCKING>(a, h, s_tab);
     compute_window<INTERLEAVED, CYL>(a, pl, cy, inc, org, nrm, p0, p1, dbase, s_red, &s_win);
     const Window win = s_win;
+    tl.mark(2);
     unsigned next_item = 0u;
     PrimSums prim_sums = {{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}};               // this wave's rectangle gradients (see block_adjoint)
   for (int pass = 0; pass < win.npass; ++pass) {
@@ -2098,6 +2140,7 @@ __device__ __forceinline__ void trace_bwd_item(const TraceArgs& a, const float* 
     }
     if (tid < 2) gtile[a.tile_cap + tid] = 0.0f;
     __syncthreads();
+    tl.mark(3); tl.mark(4);     // (backward phases: window, staging of dL/dflux, -, trace, -)
 
     const float kI = (a.mag * a.k_ext) * a.k_refl;
     float sx = 0.0f, sz = 0.0f;
@@ -2197,7 +2240,7 @@ __device__ __forceinline__ void trace_bwd_item(const TraceArgs& a, const float* 
             if (__builtin_expect((__builtin_amdgcn_ballot_w64(valid) & ~__builtin_amdgcn_ballot_w64(inwin)) != 0ull, 0)) {
                 const bool on = (tbe + 1.0f < Wf) && (tbu + 1.0f < Hf);
                 const bool in_union = (unsigned)le < twm1 && (unsigned)(iu - win.u0) < uthm1;
-                if (first && valid && on && !in_union) {              // stray: global gather, once
+                if (!diag::kNoStrays && first && valid && on && !in_union) {              // stray: global gather, once
                     const float* g_hi = G + (int64_t)(a.Hh - 2 - iu) * a.W + ie;
                     const float* g_lo = g_hi + a.W;
                     g1 = g_hi[0]; g2 = g_hi[1]; g3 = g_lo[1]; g4 = g_lo[0];
@@ -2314,6 +2357,8 @@ __device__ __forceinline__ void trace_bwd_item(const TraceArgs& a, const float* 
     }
     if (tid == 0 && pass == win.npass - 1) *s_next = (int)(gridDim.x + next_item);
     __syncthreads();   // every wave is done with this band before it is overwritten
+    tl.mark(5); tl.mark(6);
+    tl.span(7);
   }
     if (win.npass < 1 && tid == 0) *s_next = (int)(gridDim.x + fetch_work_item(work_counter, a));   // (never: npass >= 1)
     if constexpr (BLOCKING) {
@@ -2396,6 +2441,8 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     const float4* __restrict__ nrm = a.normals + (int64_t)h * a.P;
     const int64_t dbase = (int64_t)h * a.sh + (int64_t)r0 * a.sr;
 
+    diag::Timeline tl;
+    tl.begin(bwd_timeline_slot(a, item));
     const int n_prims = load_prims<BLOCKING>(a, h, s_tab);
     if (a.win_table != nullptr && queue_item >= 0) {       // the launch came with its items' windows (window_table_kernel)
         if (tid == 0) s_win = static_cast<const Window*>(a.win_table)[queue_item];
@@ -2403,6 +2450,7 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     } else
     compute_window<INTERLEAVED, CYL>(a, pl, cy, inc, org, nrm, p0, p1, dbase, s_red, &s_win);
     const Window win = s_win;
+    tl.mark(2);
     unsigned next_item = 0u;
     [[maybe_unused]] PrimSums prim_sums = {{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}};   // (blocking) this wave's rectangle gradients
     const float kI = (a.mag * a.k_ext) * a.k_refl;
@@ -2420,6 +2468,7 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     const bool packed = !CYL && a.pack_edge != 0 && win.npass == 1 && n_pts <= kPackPoints && n_pts <= kPackTrips * (int)blockDim.x &&
                         win.tw >= 2 && win.th >= 2;
     if (packed) pack_edge_points(a, pl, inc, org, nrm, p0, n_pts, win, a.pack_edge, s_edge, perm);
+    tl.mark(5);                 // (end of the edge partition; slot 5 is read out of order by tools/timeline_report.py)
     [[maybe_unused]] const unsigned wm1_bits = f32_bits(pl.wm1), hm1_bits = f32_bits(pl.hm1);
     const float lds_base = (float)(unsigned)(size_t)(lds_f32*)gtile;
     const float e0f = (float)win.e0, tw4f = (float)(4 * win.tw), u0f = (float)win.u0;
@@ -2443,6 +2492,7 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     const unsigned long long win_ok = (win.tw >= 2 && pth >= 2) ? ~0ull : 0ull;
     if (win_ok == 0ull && tid < 2) gtile[tid] = 0.0f;
     __syncthreads();
+    if (first) { tl.mark(3); tl.mark(4); }      // (window + edge partition | staging | trace)
 
     const float pu0f = (float)pu0;
     const unsigned thm2_bits = f32_bits((float)(pth - 2));
@@ -2526,7 +2576,7 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
             const lds_f32* up = (const lds_f32*)(size_t)(addr_lo + tw4);
             float g1 = up[0], g2 = up[1], g3 = lo[1], g4 = lo[0];
             unsigned long long m_use = m_in;
-            if (__builtin_expect((m_valid & ~m_in) != 0ull, 0)) {
+            if (!diag::kNoStrays && __builtin_expect((m_valid & ~m_in) != 0ull, 0)) {
                 // valid, outside this pass's window: a stray of the union window gathers from global memory, once
                 const bool valid = (m_valid >> lane) & 1ull, inwin = (m_in >> lane) & 1ull;
                 const bool on = (tbe + 1.0f < Wf) && (tbu + 1.0f < Hf);
@@ -2691,6 +2741,8 @@ __device__ __forceinline__ void trace_bwd_item_lean(const TraceArgs& a, const fl
     if (tid == 0 && pass == win.npass - 1) *s_next = (int)(gridDim.x + next_item);
     __syncthreads();
   }
+    tl.mark(6);
+    tl.span(7);
     if constexpr (BLOCKING) {          // the waves' rectangle gradients in wave order, then this item's slab (see trace_bwd_item)
         for (int w = 0; w < nwaves; ++w) {
             if (wave == w && lane < 2 * n_prims) {
@@ -3543,6 +3595,7 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
 #undef ART_LAUNCH_FWD_TYPE
 #undef ART_LAUNCH_FWD
         ART_HIP(hipGetLastError());
+        ART_HIP(diag::dump_timeline("ART_TIMELINE_OUT", items, stream));
         if (launch_lean) { const int rc = launch_lean(); if (rc != ART_OK) return rc; }
     } else {
         if (Tc > 0 || blocking) return ART_EUNSUPPORTED;   // the global-atomic A/B variant: planar, no blocking
@@ -3753,6 +3806,7 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
 #undef ART_LAUNCH_BWD_BL
 #undef ART_LAUNCH_BWD
         ART_HIP(hipGetLastError());
+        ART_HIP(diag::dump_timeline("ART_TIMELINE_OUT_BWD", items, stream));
         if (launch_lean) { const int rc = launch_lean(); if (rc != ART_OK) return rc; }
         if (blocking) {
             if (side.s) { side.s->end(); side.s = nullptr; }        // (the lean launch wrote no slabs, but `stream` must own what follows)

@@ -409,3 +409,21 @@ def test_trace_bwd_accepts_the_reported_scratch_size_on_the_host():
                         need = lib.art_trace_bwd_scratch_need(H, R, P, facet, T, Tc, Cmax)
                         whole = H * min(Cmax, 32) * 12 + (H * (Cmax - 31) * 24 if Cmax > 32 else 0)     # the least any geometry needs
                         assert call(H, R, P, facet, T, Tc, Cmax, min(need, whole) - 1) == ART_EINVAL
+
+
+def test_diagnostic_switches_live_in_one_header_only():
+    """The shipped sources carry no build-time variants: no `.hip` under artist_amd/csrc has a preprocessor conditional,
+    trace_diag.hpp is the only header there with a conditional on an ART_ macro (the diagnostic hooks, empty in the product), and
+    a plain `make` defines none of the switches."""
+    import re
+    import subprocess
+    csrc = pathlib.Path(__file__).resolve().parent.parent / "artist_amd" / "csrc"
+    hips = sorted(csrc.glob("*.hip"))
+    assert hips
+    for f in hips:
+        assert [ln for ln in f.read_text().splitlines() if ln.startswith("#if")] == [], f.name
+    conditional = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b.*\bART_", re.M)
+    assert [f.name for f in sorted(csrc.glob("*.hpp")) if conditional.search(f.read_text())] == ["trace_diag.hpp"]
+    # -B: every recipe is printed whatever has been built already; -n: nothing runs
+    recipes = subprocess.run(["make", "-n", "-B"], cwd=csrc, check=True, capture_output=True, text=True).stdout
+    assert "hipcc" in recipes and "-DART_" not in recipes

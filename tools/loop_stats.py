@@ -26,8 +26,8 @@ SRC = (ROOT / "artist_amd" / "csrc" / "trace_kernels.hip").read_text()
 
 
 def ring_depth(macro):
-    """The ring depth of the shipped source: tools/strip_variants.py left it as a comment, "// ring depth = 8: ..." /
-    "// ring depth bwd = 2: ..." (the instrumented copy under tools/diag/ still has the #define)."""
+    """The ring depth of the shipped source, which states it in a comment: "// ring depth = 8: ..." /
+    "// ring depth bwd = 2: ..." (a source that still has the #define of rounds 1-3 is read as well)."""
     words = macro[4:].lower().replace("_", " ")
     m = re.search(r"//\s*" + words + r"\s*=\s*(\d+)", SRC) or re.search(r"#define\s+" + macro + r"\s+(\d+)", SRC)
     return int(m.group(1)) if m else 8

@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Share of stray rays (valid, on the bitmap, outside the workgroup's LDS window) per heliostat of the bench field.
-Needs the diagnostic build artist_amd/libablate_COUNT_STRAYS.so (-DART_DEBUG_COUNT_STRAYS) via ARTIST_HIP_LIB."""
-import sys, pathlib, json
+Needs the diagnostic build tools/bin/libdiag_countstrays.so via ARTIST_HIP_LIB (artist_amd/csrc/trace_diag.hpp):
+  make -C artist_amd/csrc -j16 DIAG=-DART_DEBUG_COUNT_STRAYS OBJDIR=../../tools/bin/obj_countstrays OUT=../../tools/bin/libdiag_countstrays.so"""
+import os, sys, pathlib, json
+# the count is taken in the GENERIC forward item only (the lean item, the default for this field, does not count): select it,
+# which the library allows in debug mode
+os.environ["ARTIST_HIP_DEBUG"] = "1"
+os.environ["ARTIST_HIP_LEAN"] = "0"
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 import torch
 from artist_amd import ops

@@ -1,5 +1,8 @@
 """Per-item record of the LEAN forward item in a -DART_DEBUG_TIMELINE build (tools/timeline.sh): duration, stray rays, un-park
-events and window size against the item's place in the queue.  usage: python tools/timeline_lean_report.py /tmp/timeline.bin"""
+events and window size against the item's place in the queue.  usage: python tools/timeline_lean_report.py tools_out/timeline.bin
+(the stamps are the hooks of artist_amd/csrc/trace_diag.hpp, record layout there).  Moved since round 3: a launch that comes
+with its items' windows (window_table_kernel) reads its window from the table, so stamp 2 - the end of the window phase - closes
+the clearing of the tile and that read, no longer a pass over the block's points."""
 import sys
 
 import numpy as np

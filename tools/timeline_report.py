@@ -1,4 +1,9 @@
-"""Phase medians of the forward workgroups recorded by a -DART_DEBUG_TIMELINE build (tools/timeline.sh)."""
+"""Phase medians of the work items recorded by a -DART_DEBUG_TIMELINE build (tools/timeline.sh; the stamps are the hooks of
+artist_amd/csrc/trace_diag.hpp, record layout there).  Forward, generic item: the five phases named below.  Generic backward
+item: window, staging of dL/dflux, -, trace, -.  The lean backward item stamps slot 5 at the end of its edge partition, before
+slots 3 and 4: its records are recognised by that order and reported with their own phases (window, edge partition, staging,
+trace).  Moved since round 3: a lean backward launch that comes with its items' windows (window_table_kernel) reads its window
+from the table, so its "window" phase is the rectangle tables + that read, no longer a pass over the block's points."""
 import sys
 
 import numpy as np
@@ -15,6 +20,11 @@ place = (xcc.astype(np.int64) << 16) | (se.astype(np.int64) << 8) | (sh.astype(n
 t = rec[:, 1:7].astype(np.int64) * 10          # ns (100 MHz counter)
 names = ["window (phase 1)", "zero the tile", "first group of 4 samples (load latency + trace)", "rest of the trace",
          "flush"]
+trace_phase = 3
+if (rec[:, 5] >= rec[:, 2]).all() and (rec[:, 5] <= rec[:, 3]).all():      # lean backward item: slot 5 = end of the edge partition
+    t = rec[:, [1, 2, 5, 3, 6, 6]].astype(np.int64) * 10                   # (last column: the end, as for the other items)
+    names = ["window (phase 1)", "edge partition", "staging of dL/dflux", "trace"]
+    trace_phase = 3
 print(f"{len(rec)} workgroups on {len(np.unique(place))} CUs; kernel span {(t[:, 5].max() - t[:, 0].min()) / 1e6:.3f} ms")
 dur = np.diff(t, axis=1)
 for k, name in enumerate(names):
@@ -52,10 +62,6 @@ if len(idx) >= 20:
     print("      shader clock by decile (MHz): " + " ".join(f"{mhz[d].mean():.0f}" for d in dec))
     start = (t[:, 0] - t[:, 0].min()) / 1e3
     print("      item start by decile (us after the first): " + " ".join(f"{start[d].mean():.0f}" for d in dec))
-    trace_d = dur[:, 3] / 1e3
+    trace_d = dur[:, trace_phase] / 1e3
     print("      trace phase by decile (us): " + " ".join(f"{trace_d[d].mean():.0f}" for d in dec))
     print("      window phase by decile (us): " + " ".join(f"{(dur[:, 0] / 1e3)[d].mean():.1f}" for d in dec))
-    if (rec[:, 5] > rec[:, 2]).all() and (rec[:, 5] < rec[:, 3]).all():      # lean backward item: slot 5 = end of the edge partition
-        pk = (rec[:, 5].astype(np.int64) - rec[:, 2].astype(np.int64)) * 10 / 1e3
-        st = (rec[:, 3].astype(np.int64) - rec[:, 5].astype(np.int64)) * 10 / 1e3
-        print(f"      lean backward item: edge partition median {np.median(pk):.2f} us, staging of dL/dflux median {np.median(st):.2f} us")
