@@ -90,6 +90,7 @@ _BY_HEADER = {
     },
     "artist_hip_sampler.h": {
         "art_sample_distortions": (_c_int, [_c_i64, _ptr, _c_i64, _c_i64, _c_i64, _c_flt, _c_flt, _c_flt, _c_flt, _c_flt, _ptr, _ptr]),
+        "art_sample_radial_distortions": (_c_int, [_c_i64, _ptr, _c_i64, _c_i64, _c_i64, _c_flt, _c_flt, _ptr, _c_i64, _ptr, _ptr]),
     },
     "artist_hip_regularizers.h": {
         "art_surface_regularizers_fwd": (_c_int, [_ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
@@ -104,30 +105,11 @@ _BY_HEADER = {
                                          _c_int, _c_int, _c_int, _c_i64, _c_dbl, _c_i64, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_int, _c_int, _c_int,
                                          _c_dbl, _c_i64, _c_dbl, _c_int, _c_i64, _c_dbl, _c_dbl, _ptr]),
     },
-}
-
-SIGNATURES = {name: signature for table in _BY_HEADER.values() for name, signature in table.items()}
-HEADERS = {header: tuple(table) for header, table in _BY_HEADER.items()}
-
-# Entry points added since the lists above were pinned, by their header under include/extensions/: same form, bound by bind()
-# and called through call() like the rest, each header compared with its declarations by a test of its own.
-_BY_EXTENSION_HEADER = {
-    "extensions/artist_hip_sunshape.h": {
-        "art_sample_radial_distortions": (_c_int, [_c_i64, _ptr, _c_i64, _c_i64, _c_i64, _c_flt, _c_flt, _ptr, _c_i64, _ptr, _ptr]),
-    },
-}
-
-EXTENSION_SIGNATURES = {name: signature for table in _BY_EXTENSION_HEADER.values() for name, signature in table.items()}
-EXTENSION_HEADERS = {header: tuple(table) for header, table in _BY_EXTENSION_HEADER.items()}
-
-# Entry points of the headers under include/modules/: one table for the whole directory (a new module is a new header and a new
-# key here), compared with whatever headers the directory holds by tests/test_canting_host.py.
-_BY_MODULE_HEADER = {
-    "modules/artist_hip_canting.h": {
+    "artist_hip_canting.h": {
         "art_cant_facets_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
         "art_cant_facets_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
     },
-    "modules/artist_hip_shading.h": {
+    "artist_hip_shading.h": {
         "art_shading_cull": (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_i64, _c_dbl, _c_i64, _ptr, _ptr, _ptr]),
         "art_shading_prims_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr]),
         "art_shading_prims_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr]),
@@ -135,8 +117,8 @@ _BY_MODULE_HEADER = {
     },
 }
 
-MODULE_SIGNATURES = {name: signature for table in _BY_MODULE_HEADER.values() for name, signature in table.items()}
-MODULE_HEADERS = {header: tuple(table) for header, table in _BY_MODULE_HEADER.items()}
+SIGNATURES = {name: signature for table in _BY_HEADER.values() for name, signature in table.items()}
+HEADERS = {header: tuple(table) for header, table in _BY_HEADER.items()}
 
 _LIB = None
 
@@ -153,9 +135,9 @@ def build(verbose: bool = False) -> pathlib.Path:
 
 
 def bind(handle: ctypes.CDLL, path) -> ctypes.CDLL:
-    """Give every entry point of ``SIGNATURES``, ``EXTENSION_SIGNATURES`` and ``MODULE_SIGNATURES`` its types on ``handle`` (a build of the
-    library loaded from ``path``) and check the ABI version."""
-    for name, (restype, argtypes) in {**SIGNATURES, **EXTENSION_SIGNATURES, **MODULE_SIGNATURES}.items():
+    """Give every entry point of ``SIGNATURES`` its types on ``handle`` (a build of the library loaded from ``path``) and check the
+    ABI version."""
+    for name, (restype, argtypes) in SIGNATURES.items():
         try:
             fn = getattr(handle, name)
         except AttributeError as exc:

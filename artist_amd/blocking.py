@@ -77,7 +77,7 @@ def create_blocking_primitives_rectangle(blocking_heliostats_surface_points: tor
 
 class ShadingTables(torch.autograd.Function):
     """The sheared tables ``(corners [H*S,4,4], spans [H*S,2,4], normals [H*S,4])`` of the rectangles listed in ``shader_idx``
-    ``[H,S]`` (``art_shading_prims_fwd`` / ``_bwd``, include/modules/artist_hip_shading.h), differentiable w.r.t.
+    ``[H,S]`` (``art_shading_prims_fwd`` / ``_bwd``, include/artist_hip_shading.h), differentiable w.r.t.
     ``prim_corners`` through the shader's corners and through the shaded heliostat's own plane; ``incident`` is a constant."""
 
     @staticmethod

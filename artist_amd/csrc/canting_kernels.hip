@@ -1,4 +1,4 @@
-// canting_kernels.hip - art_cant_facets_fwd / _bwd (include/modules/artist_hip_canting.h): the facet canting rotation and the
+// canting_kernels.hip - art_cant_facets_fwd / _bwd (include/artist_hip_canting.h): the facet canting rotation and the
 // facet translation (artist/geometry/transforms.py:276-347, artist/nurbs/surfaces.py:674-687) as an operation of their own,
 // so that the canting vectors and the translations can learn.  The fused evaluation (nurbs_kernels.hip: finish_point /
 // point_adjoint) treats both as constants; this file repeats its arithmetic operation by operation - the forward's bits are
@@ -14,7 +14,7 @@
 
 #include "launch_common.hpp"
 
-#include "../../include/modules/artist_hip_canting.h"
+#include "../../include/artist_hip_canting.h"
 #include "canting_basis.hpp"
 
 namespace art {

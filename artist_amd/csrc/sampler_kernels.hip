@@ -1,5 +1,5 @@
-// sampler_kernels.hip - art_sample_distortions (include/artist_hip_sampler.h) and art_sample_radial_distortions
-// (include/extensions/artist_hip_sunshape.h): the sun-shape distortion sample of a light source, rows of [H,R,P] (u, e) pairs
+// sampler_kernels.hip - art_sample_distortions and art_sample_radial_distortions (include/artist_hip_sampler.h):
+// the sun-shape distortion sample of a light source, rows of [H,R,P] (u, e) pairs
 // written as one interleaved [n_rows,R,P,2] buffer in one launch.
 //
 // Counter-based: pair j of heliostat row `row` is Philox4x32-10(counter (j, row), key seed) followed by the shape's rule
@@ -8,7 +8,6 @@
 #include "launch_common.hpp"
 
 #include "../../include/artist_hip_sampler.h"
-#include "../../include/extensions/artist_hip_sunshape.h"
 
 namespace art {
 namespace {

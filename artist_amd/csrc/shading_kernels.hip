@@ -1,4 +1,4 @@
-// shading_kernels.hip - heliostat shading through the blocking kernels (include/modules/artist_hip_shading.h).
+// shading_kernels.hip - heliostat shading through the blocking kernels (include/artist_hip_shading.h).
 //
 // Shading = the sun ray to a mirror point stopped by a neighbour before it arrives.  For heliostat h with the mirror plane
 // through c with unit normal n and the unit direction to the sun s = -incident (s.n != 0), the affine shear
@@ -38,7 +38,7 @@
 
 #include "launch_common.hpp"
 
-#include "../../include/modules/artist_hip_shading.h"
+#include "../../include/artist_hip_shading.h"
 
 namespace art {
 namespace {

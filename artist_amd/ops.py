@@ -222,7 +222,7 @@ def sample_distortions(rows, number_of_rays: int, number_of_points: int, seed: i
 
 def sample_radial_distortions(rows, number_of_rays: int, number_of_points: int, seed: int, loc, table, device) -> torch.Tensor:
     """``sample_distortions`` for a radially symmetric sun shape (``art_sample_radial_distortions``,
-    include/extensions/artist_hip_sunshape.h): same rows, layout and
+    include/artist_hip_sampler.h): same rows, layout and
     streams, the radius of a ray drawn from ``table``, the fp32 ``[K+1]`` quantile table of squared radii that
     ``artist_amd.scene.radial_quantile_table`` builds, ``1 <= K <= 4096``.
 
@@ -588,7 +588,7 @@ class NurbsEval(torch.autograd.Function):
 class CantFacets(torch.autograd.Function):
     """The canting rotation of ``points`` and ``normals`` ``[H,F,M,4]`` (either may be None) by the facet bases of ``canting``
     ``[H,F,2,4]``, plus ``translations`` ``[H,F,4]`` (or None) on the points (artist/geometry/transforms.py:276-347,
-    artist/nurbs/surfaces.py:674-687; ``art_cant_facets_fwd`` / ``_bwd``, include/modules/artist_hip_canting.h).
+    artist/nurbs/surfaces.py:674-687; ``art_cant_facets_fwd`` / ``_bwd``, include/artist_hip_canting.h).
     Differentiable w.r.t. all four tensors; the backward is ONE launch that forms only the gradients asked for."""
 
     @staticmethod

@@ -2,18 +2,13 @@
  * artist_hip_canting.h - the facet canting rotation on its own, with its gradients, in libartist_hip.so (same library, same
  * conventions and return codes as include/artist_hip.h: device pointers, contiguous fp32, `stream` is a hipStream_t passed
  * as void*, asynchronous).
- *
- * Headers under include/modules/ declare entry points added after the entry-point lists of include/ and
- * include/extensions/ were pinned: those lists and the ABI version stay as they are.  The binding keeps one table for this
- * directory (artist_amd/_lib.py: MODULE_HEADERS) and tests/test_canting_host.py compares it with whatever headers the
- * directory holds, so the next module is a new file here, not a new directory.
  */
 #ifndef ARTIST_HIP_CANTING_H
 #define ARTIST_HIP_CANTING_H
 
 #include <stdint.h>
 
-#include "../artist_hip.h"
+#include "artist_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

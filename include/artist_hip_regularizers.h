@@ -1,8 +1,6 @@
 /*
  * artist_hip_regularizers.h - the surface regularisers of libartist_hip.so (same library, same conventions and return codes
  * as include/artist_hip.h: device pointers, `stream` is a hipStream_t passed as void*, asynchronous).
- *
- * Kept in a header of its own so that the entry-point list and ABI version of artist_hip.h stay as they are.
  */
 #ifndef ARTIST_HIP_REGULARIZERS_H
 #define ARTIST_HIP_REGULARIZERS_H

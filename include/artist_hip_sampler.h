@@ -1,10 +1,7 @@
 /*
- * artist_hip_sampler.h - the sun-shape distortion sampler of libartist_hip.so (same library, same conventions and
- * return codes as include/artist_hip.h: device pointers, `stream` is a hipStream_t passed as void*, asynchronous).
- *
- * Kept in a header of its own so that the entry-point list and ABI version of artist_hip.h stay as they are.  For the
- * same reason the sampler of the radially symmetric sun shapes (pillbox, Buie, tabulated: art_sample_radial_distortions) is
- * declared in extensions/artist_hip_sunshape.h, and this header's list stays as it is.
+ * artist_hip_sampler.h - the sun-shape distortion samplers of libartist_hip.so, Gaussian and radially symmetric (same
+ * library, same conventions and return codes as include/artist_hip.h: device pointers, `stream` is a hipStream_t passed as
+ * void*, asynchronous).
  */
 #ifndef ARTIST_HIP_SAMPLER_H
 #define ARTIST_HIP_SAMPLER_H
@@ -39,6 +36,34 @@ extern "C" {
 int art_sample_distortions(int64_t seed, const int64_t *rows, int64_t n_rows, int64_t R, int64_t P,
                            float loc_u, float loc_e, float l00, float l10, float l11,
                            float *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * art_sample_radial_distortions - the same sample for a radially symmetric sun shape (pillbox, Buie, a measured
+ *   profile: artist_amd.scene.Sun) given as a quantile table of squared radii.
+ *
+ *   table [K+1] fp32 (device), non-decreasing: table[k] is the squared angular radius (rad^2) below which the
+ *   fraction k/K of the energy lies; between two nodes theta^2 is linear in the quantile, which is K annuli of
+ *   equal energy with constant radiance inside each.  A uniform disc is exact with K = 1, table = {0, theta_max^2}.
+ *
+ *   Stream, counter layout, key, ray order, odd tail, output layout, the float4 / float2 store paths and the
+ *   argument checks are those of art_sample_distortions (above).  Per ray, from the same 32-bit pair (x_even, x_odd):
+ *   q = x_even * 2^-32 + 2^-33 (fp32, in (0, 1]), b = x_odd * 2^-32, t = q * K, i = min((int)t, K-1), f = t - i,
+ *   theta = sqrt(table[i] + f * (table[i+1] - table[i])) (fp32, the product and the sum rounded separately),
+ *   u = loc_u + theta cos 2 pi b, e = loc_e + theta sin 2 pi b: the radius has the table's law, the azimuth is
+ *   uniform, and (u, e) are read as small angles like the Gaussian's (relative error O(theta^2)).
+ *
+ *   Every workgroup copies the table into LDS once, as K pairs (table[i], table[i+1] - table[i]) of 8 bytes (32 KiB
+ *   at K = 4096), before its first lookup; the lookup is one 8-byte LDS read.  The bits of a row depend on
+ *   (seed, row, R, P, loc, table) only: not on the launch, the order of `rows` or the other rows of the call.
+ *   loc comes in as host scalars, the table stays on the device: nothing is read back, and no state is kept.
+ *
+ *   rows  [n_rows] int64 (device), any values;  out [n_rows,R,P,2] fp32 (device, 8-byte aligned).
+ *   ART_EINVAL for negative sizes, for K < 1 or K > 4096 (whatever the other sizes), or for null pointers (rows,
+ *   table, out) when n_rows*R*P > 0; n_rows*R*P == 0 launches nothing.
+ */
+int art_sample_radial_distortions(int64_t seed, const int64_t *rows, int64_t n_rows, int64_t R, int64_t P,
+                                  float loc_u, float loc_e, const float *table, int64_t K,
+                                  float *out, void *stream);
 
 #ifdef __cplusplus
 }

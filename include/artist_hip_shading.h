@@ -2,17 +2,13 @@
  * artist_hip_shading.h - heliostat shading as blocking by per-heliostat sheared rectangles, in libartist_hip.so (same library,
  * same conventions and return codes as include/artist_hip.h: device pointers, contiguous fp32 / int32, `stream` is a
  * hipStream_t passed as void*, asynchronous, no allocation).
- *
- * A module header (see artist_hip_canting.h): the entry-point lists of include/ and include/extensions/ and the ABI version stay
- * as they are; the binding's table for this directory is compared with the headers it holds by tests/test_canting_host.py, and
- * this header once more by tests/test_shading_host.py.
  */
 #ifndef ARTIST_HIP_SHADING_H
 #define ARTIST_HIP_SHADING_H
 
 #include <stdint.h>
 
-#include "../artist_hip.h"
+#include "artist_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

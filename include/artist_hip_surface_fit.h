@@ -4,8 +4,6 @@
  * codes as include/artist_hip.h: fp32 device pointers, `stream` is a hipStream_t passed as void*, asynchronous, arguments
  * checked before the first launch.
  *
- * Kept in a header of its own so that the entry-point list and ABI version of artist_hip.h stay as they are.
- *
  * Sizes: B facets, N rows of measured data per facet of which the first n_valid[b] count, a control net nu x nv of degrees
  * p, q (1..7, nu > p, nv > q) on clamped uniform knots.  ncells = (nu - p) * (nv - q) knot-span cells.
  * Limits: 1 <= N <= 16384, ncells <= 4096; everything a workgroup keeps in LDS (net, Adam moments, per-point gradients, cell

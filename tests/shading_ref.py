@@ -1,4 +1,4 @@
-"""NumPy restatement of heliostat shading (include/modules/artist_hip_shading.h), evaluated in the dtype it is
+"""NumPy restatement of heliostat shading (include/artist_hip_shading.h), evaluated in the dtype it is
 given (float64: the yardstick; float32: the arithmetic of the kernels, operation order not guaranteed):
 
   * the cull rule of ``art_shading_cull`` (stated at the top of artist_amd/csrc/shading_kernels.hip) with, for every pair,

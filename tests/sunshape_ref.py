@@ -1,4 +1,4 @@
-"""numpy restatement of ``art_sample_radial_distortions`` (include/extensions/artist_hip_sunshape.h): the Philox stream of
+"""numpy restatement of ``art_sample_radial_distortions`` (include/artist_hip_sampler.h): the Philox stream of
 ``tests/philox_ref.py``, then the quantile-table rule with fp32 ``q``, ``b``, ``t`` and float64 for the rest.  Also what the
 law tests of the radial sun shapes share: Buie's formulas written down a second time, the moments and the CDF of a profile
 on a fine float64 grid of their own, and the conditions a sample of the law has to meet."""

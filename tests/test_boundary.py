@@ -20,12 +20,16 @@ EXPECTED = {
         "art_trace_bwd_scratch_need", "art_adam_step",
         "art_flux_crop_pixel_loss_fwd", "art_flux_crop_pixel_loss_bwd", "art_flux_crop_kl_loss_fwd",
         "art_flux_crop_kl_loss_bwd", "art_flux_center_of_mass", "art_flux_center_of_mass_bwd"],
-    "artist_hip_sampler.h": ["art_sample_distortions"],
+    "artist_hip_sampler.h": ["art_sample_distortions", "art_sample_radial_distortions"],
     "artist_hip_regularizers.h": ["art_surface_regularizers_fwd", "art_surface_regularizers_bwd"],
     "artist_hip_surface_fit.h": ["art_surface_fit_table_words", "art_surface_fit_prepare", "art_surface_fit_loss_grad",
                                  "art_surface_fit_run"],
+    "artist_hip_canting.h": ["art_cant_facets_fwd", "art_cant_facets_bwd"],
+    "artist_hip_shading.h": ["art_shading_cull", "art_shading_prims_fwd", "art_shading_prims_bwd", "art_shading_append"],
 }
 HEADERS = sorted(path.name for path in (ROOT / "include").glob("*.h"))
+# The only ART_ macros outside artist_hip.h: values of an argument (surface fitting's `mode`), not return codes.
+OTHER_DEFINES = {"artist_hip_surface_fit.h": ["ART_FIT_NORMALS", "ART_FIT_POINTS"]}
 
 # C type -> ctypes type, by kind: every pointer travels as c_void_p; a pointer is a return type only as `const char *`
 PARAMETER_KINDS = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float}
@@ -59,13 +63,20 @@ def test_header_declares_the_expected_entry_points():
 @pytest.mark.parametrize("header", HEADERS)
 def test_binding_mirrors_the_header(header):
     """Names, exports, and - by kind - every parameter and return type: an ``int`` bound where the header says ``int64_t``, or a
-    pointer where it says ``double``, corrupts arguments on the way to the device instead of raising."""
+    pointer where it says ``double``, corrupts arguments on the way to the device instead of raising.  The public headers are
+    the files directly under include/: no entry point is declared in two of them, and the return codes are artist_hip.h's."""
     from artist_amd import _lib
     assert sorted(_lib.HEADERS) == HEADERS == sorted(EXPECTED)
+    assert [path for path in (ROOT / "include").rglob("*.h") if path.parent != ROOT / "include"] == []
+    declared = [name for h in HEADERS for name in header_functions(h)]
+    assert len(declared) == len(set(declared)), sorted(name for name in set(declared) if declared.count(name) > 1)
+    if header != "artist_hip.h":
+        assert sorted(re.findall(r"#define\s+(ART_\w+)", header_text(header))) == OTHER_DEFINES.get(header, [])
+        assert '#include "artist_hip.h"' in header_text(header)
     assert sum(len(names) for names in _lib.HEADERS.values()) == len(_lib.SIGNATURES)          # no name under two headers
     assert {name for names in _lib.HEADERS.values() for name in names} == set(_lib.SIGNATURES)
     protos = header_prototypes(header)
-    assert sorted(protos) == header_functions(header) == sorted(_lib.HEADERS[header]) == sorted(EXPECTED[header])
+    assert protos and sorted(protos) == header_functions(header) == sorted(_lib.HEADERS[header]) == sorted(EXPECTED[header])
     exported = ctypes.CDLL(str(_lib.LIB_PATH))
     lib = _lib.lib()                       # no compute call: loading + version query only
     for name, (restype, argtypes) in protos.items():
@@ -79,7 +90,7 @@ def test_binding_mirrors_the_header(header):
     assert defines == {name: value for name, value in vars(_lib).items() if name == "ART_OK" or name.startswith("ART_E")}
     assert sorted(defines) == sorted(["ART_OK", "ART_EINVAL", "ART_ETARGET", "ART_ELAUNCH", "ART_EUNSUPPORTED", "ART_ECANDIDATES",
                                       "ART_EQUEUE"])
-    assert lib.art_abi_version() == _lib.ABI_VERSION
+    assert lib.art_abi_version() == _lib.ABI_VERSION == 13
     assert lib.art_strerror(_lib.ART_OK) == b"ok" and b"invalid" in lib.art_strerror(_lib.ART_EINVAL)
 
 

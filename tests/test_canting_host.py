@@ -1,6 +1,6 @@
 """Host side of the facet canting: the numpy restatement (tests/canting_ref.py) against the reference's outputs in
-tests/golden/canting.npz (generate_canting_golden.py), the binding of the headers under include/modules/, and the argument
-checks of art_cant_facets_fwd / _bwd (include/modules/artist_hip_canting.h)."""
+tests/golden/canting.npz (generate_canting_golden.py), and the argument checks of art_cant_facets_fwd / _bwd
+(include/artist_hip_canting.h)."""
 import ctypes
 
 import numpy as np
@@ -8,10 +8,7 @@ import pytest
 import torch
 
 import canting_ref as ref
-import test_boundary
 from conftest import rel_l2
-
-ART_EINVAL = -1                                                   # include/artist_hip.h
 
 
 def _max_close(got, want, rel):
@@ -77,31 +74,6 @@ def test_the_fixture_holds_what_the_tests_need(golden):
     assert (np.abs((b[:, 0] * b[:, 1]).sum(-1)) > 0.05).all()      # n not orthogonal to e
 
 
-def test_binding_mirrors_the_module_headers():
-    """tests/test_boundary.py::test_binding_mirrors_the_header for whatever headers include/modules/ holds: names, exports and,
-    by kind, every parameter and return type; no name in two tables; the ABI version as it was."""
-    from artist_amd import _lib
-    found = sorted(f"modules/{path.name}" for path in (test_boundary.ROOT / "include" / "modules").glob("*.h"))
-    assert found and sorted(_lib.MODULE_HEADERS) == found
-    tables = (_lib.SIGNATURES, _lib.EXTENSION_SIGNATURES, _lib.MODULE_SIGNATURES)
-    assert sum(len(t) for t in tables) == len(set().union(*tables))                 # no name in two tables
-    assert sum(len(names) for names in _lib.MODULE_HEADERS.values()) == len(_lib.MODULE_SIGNATURES)
-    assert {name for names in _lib.MODULE_HEADERS.values() for name in names} == set(_lib.MODULE_SIGNATURES)
-    exported, lib = ctypes.CDLL(str(_lib.LIB_PATH)), _lib.lib()
-    for header in found:
-        protos = test_boundary.header_prototypes(header)
-        assert protos and sorted(protos) == test_boundary.header_functions(header) == sorted(_lib.MODULE_HEADERS[header])
-        for name, (restype, argtypes) in protos.items():
-            assert hasattr(exported, name), f"{name} missing from {_lib.LIB_PATH}"
-            assert _lib.MODULE_SIGNATURES[name] == (restype, argtypes), name
-            bound = getattr(lib, name)
-            assert (bound.restype, list(bound.argtypes)) == (restype, argtypes), name
-        text = test_boundary.header_text(header)
-        assert "#define ART_" not in text and '#include "../artist_hip.h"' in text    # the return codes are artist_hip.h's
-    assert "art_cant_facets_fwd" in _lib.MODULE_SIGNATURES and "art_cant_facets_bwd" in _lib.MODULE_SIGNATURES
-    assert lib.art_abi_version() == _lib.ABI_VERSION == 13
-
-
 def test_canting_argument_checks_need_no_device():
     from artist_amd import _lib
     fwd, bwd = _lib.lib().art_cant_facets_fwd, _lib.lib().art_cant_facets_bwd
@@ -114,24 +86,24 @@ def test_canting_argument_checks_need_no_device():
     assert bwd(None, None, None, None, None, 0, 4, 0, p, None, None, None, None) == 0     # (no sum requested: nothing to zero)
     # negative or oversized sizes, whatever the pointers
     for HF, M in ((-1, 35), (4, -1), (1 << 31, 1), (1, 1 << 31)):
-        assert fwd(p, None, p, p, 0, HF, M, p, p, None) == ART_EINVAL, (HF, M)
-        assert bwd(p, p, p, p, p, 0, HF, M, p, p, p, None, None) == ART_EINVAL, (HF, M)
+        assert fwd(p, None, p, p, 0, HF, M, p, p, None) == _lib.ART_EINVAL, (HF, M)
+        assert bwd(p, p, p, p, p, 0, HF, M, p, p, p, None, None) == _lib.ART_EINVAL, (HF, M)
     # forward: null pointers with work to do
-    assert fwd(None, None, p, p, 0, 4, 35, p, p, None) == ART_EINVAL         # no canting
-    assert fwd(p, None, None, None, 0, 4, 35, p, p, None) == ART_EINVAL      # no data at all
-    assert fwd(p, None, p, None, 0, 4, 35, None, p, None) == ART_EINVAL      # points without their output
-    assert fwd(p, None, None, p, 0, 4, 35, p, None, None) == ART_EINVAL      # normals without their output
-    assert fwd(p, p, None, p, 0, 4, 35, None, p, None) == ART_EINVAL         # translations without points
-    assert fwd(p, p, p, None, 1, 4, 35, p, None, None) == ART_EINVAL         # translations with the inverse
+    assert fwd(None, None, p, p, 0, 4, 35, p, p, None) == _lib.ART_EINVAL         # no canting
+    assert fwd(p, None, None, None, 0, 4, 35, p, p, None) == _lib.ART_EINVAL      # no data at all
+    assert fwd(p, None, p, None, 0, 4, 35, None, p, None) == _lib.ART_EINVAL      # points without their output
+    assert fwd(p, None, None, p, 0, 4, 35, p, None, None) == _lib.ART_EINVAL      # normals without their output
+    assert fwd(p, p, None, p, 0, 4, 35, None, p, None) == _lib.ART_EINVAL         # translations without points
+    assert fwd(p, p, p, None, 1, 4, 35, p, None, None) == _lib.ART_EINVAL         # translations with the inverse
     # backward
-    assert bwd(p, p, p, p, p, 0, 4, 35, None, None, None, None, None) == ART_EINVAL      # no output requested
-    assert bwd(p, p, p, p, p, 0, 0, 35, None, None, None, None, None) == ART_EINVAL      # ... whatever the sizes
-    assert bwd(None, p, p, p, p, 0, 4, 35, p, p, p, p, None) == ART_EINVAL               # no canting
-    assert bwd(p, p, p, None, p, 0, 4, 35, p, None, None, None, None) == ART_EINVAL      # grad_data_points without grad_out_points
-    assert bwd(p, p, p, p, None, 0, 4, 35, None, p, None, None, None) == ART_EINVAL      # grad_data_normals without grad_out_normals
-    assert bwd(p, None, p, p, p, 0, 4, 35, None, None, p, None, None) == ART_EINVAL      # grad_canting without the points
-    assert bwd(p, p, None, p, p, 0, 4, 35, None, None, p, None, None) == ART_EINVAL      # grad_canting without the normals
-    assert bwd(p, p, p, p, p, 1, 4, 35, None, None, None, p, None) == ART_EINVAL         # grad_translations with the inverse
+    assert bwd(p, p, p, p, p, 0, 4, 35, None, None, None, None, None) == _lib.ART_EINVAL      # no output requested
+    assert bwd(p, p, p, p, p, 0, 0, 35, None, None, None, None, None) == _lib.ART_EINVAL      # ... whatever the sizes
+    assert bwd(None, p, p, p, p, 0, 4, 35, p, p, p, p, None) == _lib.ART_EINVAL               # no canting
+    assert bwd(p, p, p, None, p, 0, 4, 35, p, None, None, None, None) == _lib.ART_EINVAL      # grad_data_points without grad_out_points
+    assert bwd(p, p, p, p, None, 0, 4, 35, None, p, None, None, None) == _lib.ART_EINVAL      # grad_data_normals without grad_out_normals
+    assert bwd(p, None, p, p, p, 0, 4, 35, None, None, p, None, None) == _lib.ART_EINVAL      # grad_canting without the points
+    assert bwd(p, p, None, p, p, 0, 4, 35, None, None, p, None, None) == _lib.ART_EINVAL      # grad_canting without the normals
+    assert bwd(p, p, p, p, p, 1, 4, 35, None, None, None, p, None) == _lib.ART_EINVAL         # grad_translations with the inverse
 
 
 def test_perform_canting_is_exported_and_has_no_cpu_fallback():

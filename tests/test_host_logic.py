@@ -397,18 +397,17 @@ def test_trace_bwd_accepts_the_reported_scratch_size_on_the_host():
                                  1.0, 1.0, 0.935, H, R, P, facet, T, Tc, 256, 256, 0, fake, fake, fake,
                                  *([fake if Cmax else null] * 3), fake, scratch_floats, null)
 
-    ART_EINVAL = -1
     for R, P, facet in ((100, 10000, 2500), (180, 3600, 900)):
         for Cmax in (0, 8, 16, 100):
             for H in (1, 3, 60, 100, 101, 313, 599):
                 reported = lib.art_trace_bwd_scratch_floats(H, R, P, facet, Cmax)
                 for T, Tc in ((1, 0), (0, 1), (1, 1)):
                     rc = call(H, R, P, facet, T, Tc, Cmax, reported)
-                    assert rc != ART_EINVAL and rc != 0, (H, R, P, facet, Cmax, T, Tc, rc)
+                    assert rc != _lib.ART_EINVAL and rc != 0, (H, R, P, facet, Cmax, T, Tc, rc)
                     if Cmax:
                         need = lib.art_trace_bwd_scratch_need(H, R, P, facet, T, Tc, Cmax)
                         whole = H * min(Cmax, 32) * 12 + (H * (Cmax - 31) * 24 if Cmax > 32 else 0)     # the least any geometry needs
-                        assert call(H, R, P, facet, T, Tc, Cmax, min(need, whole) - 1) == ART_EINVAL
+                        assert call(H, R, P, facet, T, Tc, Cmax, min(need, whole) - 1) == _lib.ART_EINVAL
 
 
 def test_diagnostic_switches_live_in_one_header_only():

@@ -9,7 +9,6 @@ import torch
 
 import regularizer_ref as ref
 
-ART_EINVAL = -1                                                   # include/artist_hip.h
 N_SHAPES = 7
 
 
@@ -86,10 +85,10 @@ def test_regularizer_argument_checks_need_no_device():
     assert fwd(None, None, 0, 6, 6, None, None, None) == 0          # no nets: no launch, no pointer needed
     assert bwd(None, None, 0, 6, 6, None, None, None, None) == 0
     for N, U, V in ((-1, 6, 6), (0, 0, 6), (4, 6, 0), (4, 53, 53), (1, 1, 2731)):   # bad sizes; nets larger than the LDS staging
-        assert fwd(None, None, N, U, V, None, None, None) == ART_EINVAL, (N, U, V)
-        assert bwd(None, None, N, U, V, None, None, None, None) == ART_EINVAL, (N, U, V)
+        assert fwd(None, None, N, U, V, None, None, None) == _lib.ART_EINVAL, (N, U, V)
+        assert bwd(None, None, N, U, V, None, None, None, None) == _lib.ART_EINVAL, (N, U, V)
     p = ctypes.c_void_p(16)                                          # (never dereferenced: every call below fails its checks)
-    assert fwd(p, p, 4, 6, 6, None, None, None) == ART_EINVAL      # neither output
-    assert fwd(None, p, 4, 6, 6, p, p, None) == ART_EINVAL
-    assert bwd(p, p, 4, 6, 6, p, p, None, None) == ART_EINVAL     # no gradient buffer
-    assert bwd(p, None, 4, 6, 6, None, None, p, None) == ART_EINVAL
+    assert fwd(p, p, 4, 6, 6, None, None, None) == _lib.ART_EINVAL      # neither output
+    assert fwd(None, p, 4, 6, 6, p, p, None) == _lib.ART_EINVAL
+    assert bwd(p, p, 4, 6, 6, p, p, None, None) == _lib.ART_EINVAL     # no gradient buffer
+    assert bwd(p, None, 4, 6, 6, None, None, p, None) == _lib.ART_EINVAL

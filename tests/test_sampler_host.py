@@ -6,7 +6,6 @@ import torch
 
 import philox_ref
 
-ART_EINVAL = -1                                                   # include/artist_hip.h
 
 
 @pytest.mark.parametrize("counter, key, expected", [
@@ -34,9 +33,9 @@ def test_sampler_argument_checks_need_no_device():
     law = (0.0, 0.0, 1.0, 0.0, 1.0)
     assert f(7, None, 0, 3, 5, *law, None, None) == 0              # nothing to draw: no launch, no pointer needed
     assert f(7, None, 4, 0, 5, *law, None, None) == 0
-    assert f(7, None, -1, 3, 5, *law, None, None) == ART_EINVAL
-    assert f(7, None, 2, 3, -5, *law, None, None) == ART_EINVAL
-    assert f(7, None, 2, 3, 5, *law, None, None) == ART_EINVAL    # null pointers with work to do
+    assert f(7, None, -1, 3, 5, *law, None, None) == _lib.ART_EINVAL
+    assert f(7, None, 2, 3, -5, *law, None, None) == _lib.ART_EINVAL
+    assert f(7, None, 2, 3, 5, *law, None, None) == _lib.ART_EINVAL    # null pointers with work to do
 
 
 def test_unknown_sampler_name_is_a_value_error():

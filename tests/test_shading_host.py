@@ -1,13 +1,10 @@
-"""Heliostat shading, the part that needs no GPU: the shear identity behind it, the C ABI's header against the binding, the
-argument checks, and the size of the approximation on a canted heliostat."""
+"""Heliostat shading, the part that needs no GPU: the shear identity behind it, the argument checks, and the size of the
+approximation on a canted heliostat."""
 import ctypes
 
 import numpy as np
 
 import shading_ref as ref
-import test_boundary
-
-ART_EINVAL = -1
 
 
 def _random_case(rng):
@@ -66,29 +63,6 @@ def test_shear_identity_in_fp64():
     assert worst < 1e-9, worst
 
 
-def test_binding_mirrors_the_shading_header():
-    """The four entry points of include/modules/artist_hip_shading.h: declared there and nowhere else, exported, and bound
-    with the header's types parameter by parameter."""
-    from artist_amd import _lib
-    header = "modules/artist_hip_shading.h"
-    names = ["art_shading_append", "art_shading_cull", "art_shading_prims_bwd", "art_shading_prims_fwd"]
-    assert sorted(_lib.MODULE_HEADERS[header]) == names
-    protos = test_boundary.header_prototypes(header)
-    assert sorted(protos) == test_boundary.header_functions(header) == names
-    assert not set(names) & (set(_lib.SIGNATURES) | set(_lib.EXTENSION_SIGNATURES))
-    for other in list(_lib.HEADERS) + list(_lib.EXTENSION_HEADERS) + [h for h in _lib.MODULE_HEADERS if h != header]:
-        assert not set(names) & set(test_boundary.header_functions(other)), other
-    exported, lib = ctypes.CDLL(str(_lib.LIB_PATH)), _lib.lib()
-    for name, (restype, argtypes) in protos.items():
-        assert hasattr(exported, name), f"{name} missing from {_lib.LIB_PATH}"
-        assert _lib.MODULE_SIGNATURES[name] == (restype, argtypes), name
-        bound = getattr(lib, name)
-        assert (bound.restype, list(bound.argtypes)) == (restype, argtypes), name
-    text = test_boundary.header_text(header)
-    assert "#define ART_" not in text and '#include "../artist_hip.h"' in text
-    assert lib.art_abi_version() == _lib.ABI_VERSION == 13
-
-
 def test_shading_argument_checks_need_no_device():
     from artist_amd import _lib
     lib = _lib.lib()
@@ -100,21 +74,21 @@ def test_shading_argument_checks_need_no_device():
     assert lib.art_shading_append(None, None, 0, 5, 8, 16, None, None, None) == 0
     # bad sizes, whatever the pointers
     for H, N, S in ((-1, 4, 8), (4, -1, 8), (4, 4, 0), (4, 4, 4097), (1 << 23, 4, 8), (4, 1 << 23, 8), (1 << 20, 4, 8)):
-        assert lib.art_shading_cull(p, p, p, H, N, 0.0, S, p, p, None) == ART_EINVAL, (H, N, S)
-        assert lib.art_shading_prims_fwd(p, p, p, p, H, N, S, p, p, p, None) == ART_EINVAL, (H, N, S)
-        assert lib.art_shading_prims_bwd(p, p, p, p, p, p, p, H, N, S, p, p, None) == ART_EINVAL, (H, N, S)
-        assert lib.art_shading_append(p, p, H, N, S, 16, p, p, None) == ART_EINVAL, (H, N, S)
-    assert lib.art_shading_cull(p, p, p, 4, 4, -1.0, 8, p, p, None) == ART_EINVAL          # the scatter bound is the caller's
-    assert lib.art_shading_cull(p, p, p, 4, 4, float("nan"), 8, p, p, None) == ART_EINVAL
-    assert lib.art_shading_append(p, p, 4, 4, 8, 0, p, p, None) == ART_EINVAL
+        assert lib.art_shading_cull(p, p, p, H, N, 0.0, S, p, p, None) == _lib.ART_EINVAL, (H, N, S)
+        assert lib.art_shading_prims_fwd(p, p, p, p, H, N, S, p, p, p, None) == _lib.ART_EINVAL, (H, N, S)
+        assert lib.art_shading_prims_bwd(p, p, p, p, p, p, p, H, N, S, p, p, None) == _lib.ART_EINVAL, (H, N, S)
+        assert lib.art_shading_append(p, p, H, N, S, 16, p, p, None) == _lib.ART_EINVAL, (H, N, S)
+    assert lib.art_shading_cull(p, p, p, 4, 4, -1.0, 8, p, p, None) == _lib.ART_EINVAL          # the scatter bound is the caller's
+    assert lib.art_shading_cull(p, p, p, 4, 4, float("nan"), 8, p, p, None) == _lib.ART_EINVAL
+    assert lib.art_shading_append(p, p, 4, 4, 8, 0, p, p, None) == _lib.ART_EINVAL
     # null pointers with work to do
-    assert lib.art_shading_cull(None, p, p, 4, 4, 0.0, 8, p, p, None) == ART_EINVAL
-    assert lib.art_shading_cull(p, p, p, 4, 4, 0.0, 8, None, p, None) == ART_EINVAL
-    assert lib.art_shading_prims_fwd(p, p, p, None, 4, 4, 8, p, p, p, None) == ART_EINVAL
-    assert lib.art_shading_prims_fwd(p, p, p, p, 4, 4, 8, ctypes.c_void_p(20), p, p, None) == ART_EINVAL    # alignment
-    assert lib.art_shading_prims_bwd(p, p, p, p, p, p, p, 4, 4, 8, None, p, None) == ART_EINVAL
-    assert lib.art_shading_prims_bwd(p, p, p, p, p, p, p, 4, 4, 8, p, None, None) == ART_EINVAL
-    assert lib.art_shading_append(p, p, 4, 4, 8, 16, None, p, None) == ART_EINVAL
+    assert lib.art_shading_cull(None, p, p, 4, 4, 0.0, 8, p, p, None) == _lib.ART_EINVAL
+    assert lib.art_shading_cull(p, p, p, 4, 4, 0.0, 8, None, p, None) == _lib.ART_EINVAL
+    assert lib.art_shading_prims_fwd(p, p, p, None, 4, 4, 8, p, p, p, None) == _lib.ART_EINVAL
+    assert lib.art_shading_prims_fwd(p, p, p, p, 4, 4, 8, ctypes.c_void_p(20), p, p, None) == _lib.ART_EINVAL    # alignment
+    assert lib.art_shading_prims_bwd(p, p, p, p, p, p, p, 4, 4, 8, None, p, None) == _lib.ART_EINVAL
+    assert lib.art_shading_prims_bwd(p, p, p, p, p, p, p, 4, 4, 8, p, None, None) == _lib.ART_EINVAL
+    assert lib.art_shading_append(p, p, 4, 4, 8, 16, None, p, None) == _lib.ART_EINVAL
 
 
 def test_cull_reference_lists_the_shaders_of_a_two_row_field():

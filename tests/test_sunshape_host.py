@@ -7,10 +7,8 @@ import pytest
 import torch
 
 import sunshape_ref
-import test_boundary
 from sunshape_ref import DISC, EXTENT
 
-ART_EINVAL = -1                                                   # include/artist_hip.h
 K = 1024
 
 
@@ -172,42 +170,20 @@ def test_hip_sampler_on_a_cpu_radial_sun_has_no_fallback():
         ops.sample_radial_distortions([0], 2, 3, 7, (0.0, 0.0), s.quantile_table, "cpu")
 
 
-def test_binding_mirrors_the_extension_header():
-    """tests/test_boundary.py::test_binding_mirrors_the_header for the headers under include/extensions/: names, exports, and
-    by kind every parameter and return type; and no name of theirs in a header directly under include/."""
-    from artist_amd import _lib
-    expected = {"extensions/artist_hip_sunshape.h": ["art_sample_radial_distortions"]}
-    found = sorted(f"extensions/{path.name}" for path in (test_boundary.ROOT / "include" / "extensions").glob("*.h"))
-    assert sorted(_lib.EXTENSION_HEADERS) == found == sorted(expected)
-    assert not set(_lib.EXTENSION_SIGNATURES) & set(_lib.SIGNATURES)
-    assert {name for names in _lib.EXTENSION_HEADERS.values() for name in names} == set(_lib.EXTENSION_SIGNATURES)
-    exported, lib = ctypes.CDLL(str(_lib.LIB_PATH)), _lib.lib()
-    for header, names in expected.items():
-        protos = test_boundary.header_prototypes(header)
-        assert sorted(protos) == test_boundary.header_functions(header) == sorted(_lib.EXTENSION_HEADERS[header]) == sorted(names)
-        for name, (restype, argtypes) in protos.items():
-            assert hasattr(exported, name), f"{name} missing from {_lib.LIB_PATH}"
-            assert _lib.EXTENSION_SIGNATURES[name] == (restype, argtypes), name
-            bound = getattr(lib, name)
-            assert (bound.restype, list(bound.argtypes)) == (restype, argtypes), name
-        assert "#define ART_" not in test_boundary.header_text(header)        # the return codes are artist_hip.h's
-    assert lib.art_abi_version() == _lib.ABI_VERSION == 13
-
-
 def test_radial_sampler_argument_checks_need_no_device():
     from artist_amd import _lib
     f = _lib.lib().art_sample_radial_distortions
     loc = (0.0, 0.0)
     assert f(7, None, 0, 3, 5, *loc, None, 1, None, None) == 0     # nothing to draw: no launch, no pointer needed
     assert f(7, None, 4, 0, 5, *loc, None, 4096, None, None) == 0
-    assert f(7, None, -1, 3, 5, *loc, None, 1, None, None) == ART_EINVAL
-    assert f(7, None, 2, 3, -5, *loc, None, 1, None, None) == ART_EINVAL
+    assert f(7, None, -1, 3, 5, *loc, None, 1, None, None) == _lib.ART_EINVAL
+    assert f(7, None, 2, 3, -5, *loc, None, 1, None, None) == _lib.ART_EINVAL
     for bad_k in (0, -1, 4097, 1 << 40):                            # K out of range, with and without work to do
-        assert f(7, None, 0, 3, 5, *loc, None, bad_k, None, None) == ART_EINVAL
-        assert f(7, None, 2, 3, 5, *loc, None, bad_k, None, None) == ART_EINVAL
-    assert f(7, None, 2, 3, 5, *loc, None, 1, None, None) == ART_EINVAL       # null pointers with work to do
+        assert f(7, None, 0, 3, 5, *loc, None, bad_k, None, None) == _lib.ART_EINVAL
+        assert f(7, None, 2, 3, 5, *loc, None, bad_k, None, None) == _lib.ART_EINVAL
+    assert f(7, None, 2, 3, 5, *loc, None, 1, None, None) == _lib.ART_EINVAL       # null pointers with work to do
     rows, out = (ctypes.c_int64 * 2)(), (ctypes.c_float * 64)()              # (never reached: the null table returns first)
-    assert f(7, ctypes.addressof(rows), 2, 3, 5, *loc, None, 1, ctypes.addressof(out), None) == ART_EINVAL
+    assert f(7, ctypes.addressof(rows), 2, 3, 5, *loc, None, 1, ctypes.addressof(out), None) == _lib.ART_EINVAL
 
 
 class Leaf:
