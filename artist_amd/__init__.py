@@ -14,6 +14,7 @@ backward, behind ARTIST's own call surface:
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer
                                     <-> artist.optim.SmoothnessRegularizer, IdealSurfaceRegularizer (the epoch's regularisers)
     artist_amd.SurfaceGenerator     <-> artist.scenario.surface_generator.SurfaceGenerator (+ fit_nurbs_batch: all facets at once)
+    artist_amd.EpochGraph           (no counterpart) an epoch captured into a HIP graph and replayed: same bits, one host call
 
 All arithmetic runs in hand-written HIP kernels (``artist_amd/csrc``) reached through the C ABI in
 ``include/artist_hip.h``; there is no CPU fallback.
@@ -30,5 +31,6 @@ from .raytracing import HeliostatRayTracer  # noqa: F401
 from .scenario import Scenario, open_scenario_file  # noqa: F401
 from .sampling import DistortionsDataset, RestrictedDistributedSampler  # noqa: F401
 from .surface_generator import FittedFacet, SurfaceGenerator  # noqa: F401
+from .graphs import EpochGraph  # noqa: F401
 
 __version__ = "0.1.0"

@@ -174,12 +174,41 @@ def check(code: int, what: str) -> None:
         raise ArtistHipError(f"{what}: {msg} (code {code}, hipError {handle.art_last_hip_error()})")
 
 
+def capturing() -> bool:
+    """Is the current stream being captured into a graph (``torch.cuda.graph``)?  Asked where a cache misses or a call
+    fails, never on a path that an epoch takes every time."""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+# Tensors that the package's caches handed to a step while artist_amd.graphs.EpochGraph captured it: their addresses are
+# baked into the graph, but a cache may drop its entry (a bounded table, a new version of its key, an error that clears the
+# accumulators) long before the graph is gone.  The graph keeps them.  None: nobody is capturing.
+_KEPT_BY_CAPTURE = None
+
+
+def keep_alive(*tensors) -> None:
+    """Called by the caches on the tensors they hand out (one comparison when no EpochGraph is capturing)."""
+    if _KEPT_BY_CAPTURE is not None:
+        _KEPT_BY_CAPTURE.extend(t for t in tensors if t is not None)
+
+
+def first_use_under_capture(what: str) -> ArtistHipError:
+    """The error for state that would have to be created, zero-initialised or read back on the host while the stream
+    is being captured - library memory, an accumulator buffer, a cache entry that needs a host read.  Nothing has been
+    created and no HIP call has failed: the capture itself is still valid."""
+    return ArtistHipError(f"{what}: first use on this stream under graph capture: run the step once on this stream before "
+                          "capturing (artist_amd.graphs.EpochGraph does)")
+
+
 def call(name: str, device, *args, on_error=check) -> None:
     """Launch entry point ``name`` on the current stream of ``device``, which goes in as the last argument (``void *stream``
     ends every launching entry point), and hand a non-zero return code to ``on_error(code, name)``.  The function is looked
     up on the handle at call time: tests wrap attributes of the handle and must see every call."""
     with torch.cuda.device(device):
         code = getattr(lib(), name)(*args, torch.cuda.current_stream(device).cuda_stream)
+        if code == ART_EUNSUPPORTED and capturing():
+            # the library creates nothing while its stream is being captured (include/artist_hip.h, Conventions)
+            raise first_use_under_capture(name)
     if code != ART_OK:
         on_error(code, name)
 

@@ -51,6 +51,8 @@ def create_blocking_primitives_rectangles_by_index(blocking_heliostats_active_su
     key = (P, pts.device)
     index = _CORNER_INDEX.get(key)
     if index is None:      # (a host list -> device tensor copy waits for the stream: once per shape, not once per trace call)
+        if _lib.capturing():
+            raise _lib.first_use_under_capture("the corner indices of the blocking rectangles")
         index = _CORNER_INDEX[key] = torch.tensor([int(P / 2), int(side - 1), int((P / 2) - 1), int(P - side)], device=pts.device)
     corners = pts.index_select(1, index)
     spans, normals = _spans_and_normals(corners)

@@ -519,6 +519,9 @@ extern "C" int art_blocking_filter(const float* origins, const float* normals, c
                    plane_normals, plane_dims, cyl_centers, cyl_normals, cyl_axes, cyl_radii, cyl_heights, cyl_opening,
                    ray_magnitude, 0.0, 1.0, H, R, P, T, Tc, W, Hh, 0))
         return ART_EINVAL;
+    // Blocking is not captured into a graph (include/artist_hip.h, Conventions): refused before anything is enqueued.
+    if (stream_is_capturing(stream)) return ART_EUNSUPPORTED;
+    const StatusWord status = status_word(stream);
     set_cone(a, max_scatter_angle);
     char* ws = static_cast<char*>(workspace);
     Beam* beams = reinterpret_cast<Beam*>(ws); ws += sizeof(Beam) * H;
@@ -578,7 +581,7 @@ extern "C" int art_blocking_filter(const float* origins, const float* normals, c
                                prim_corners, owner, cand, cand_count, (int)Cmax, live, flags);
     }
     hipLaunchKernelGGL(compact_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, stream, cand, cand_count, (int)H,
-                       (int)Cmax, flags, status_word().dev);
+                       (int)Cmax, flags, status.dev);
     ART_HIP(hipGetLastError());
     return ART_OK;
 }

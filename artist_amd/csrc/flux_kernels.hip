@@ -757,7 +757,8 @@ __global__ __launch_bounds__(kReduceBlock) void flux_crop_kl_loss_bwd_kernel(con
 using namespace art;
 
 // Scratch of the part kernels: one PartScratch per (device, stream), allocated on first use and kept (every entry is written
-// before it is read: no initialisation).  nullptr when the allocation fails: the callers give a bitmap one workgroup.
+// before it is read: no initialisation).  nullptr when the allocation fails: the callers give a bitmap one workgroup.  nullptr as
+// well, with nothing allocated, for a stream that has none yet and is being captured: the caller returns ART_EUNSUPPORTED.
 static PartScratch* flux_parts_scratch(hipStream_t stream)
 {
     struct Entry { int dev; hipStream_t stream; PartScratch* ws; };
@@ -768,6 +769,7 @@ static PartScratch* flux_parts_scratch(hipStream_t stream)
     std::lock_guard<std::mutex> guard(lock);
     for (const Entry& e : table)
         if (e.dev == dev && e.stream == stream) return e.ws;
+    if (stream_is_capturing(stream)) return nullptr;        // (the caller reports it: no one-workgroup fall-back inside a capture)
     PartScratch* ws = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&ws), sizeof(PartScratch)) != hipSuccess) return nullptr;
     table.push_back({dev, stream, ws});
@@ -870,6 +872,7 @@ extern "C" int art_flux_crop_pixel_loss_fwd(const float* flux, const float* targ
         return ART_EINVAL;
     const int P = loss_workgroups_per_bitmap(B, Hh);
     PartScratch* ws = P > 1 ? flux_parts_scratch(stream) : nullptr;
+    if (P > 1 && ws == nullptr && stream_is_capturing(stream)) return ART_EUNSUPPORTED;     // first use under capture: nothing allocated
     // LDS for the rows a part samples (a crop never magnifies by much: the rows of a part + 3 cover every scale up to 1), two
     // workgroups per CU: at most 76 KB each
     int stage_rows = (int)std::min<int64_t>(Hh, (Hh + kLossParts - 1) / kLossParts + 4);
@@ -887,9 +890,11 @@ extern "C" int art_flux_crop_pixel_loss_fwd(const float* flux, const float* targ
                            (int)W, loss, centers4, center_grad_unit, moments);
     } else
     {
-        if (stage_bytes > 48 * 1024)
-            ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&flux_crop_pixel_loss_fwd_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes));
+        if (stage_bytes > 48 * 1024) {
+            static LdsGrant granted;
+            const int rc = grant_dynamic_lds(reinterpret_cast<const void*>(&flux_crop_pixel_loss_fwd_kernel<true>), granted, stage_bytes);
+            if (rc != ART_OK) return rc;
+        }
         hipLaunchKernelGGL(flux_crop_pixel_loss_fwd_kernel<true>, dim3(1u, (unsigned)B), dim3(kReduceBlock), stage_bytes, stream, flux, target_dims,
                            ground_truth, (int)Hh, (int)W, (float)crop_width, (float)crop_height, kLossParts, (PartScratch*)nullptr, residual,
                            loss, centers4, center_grad_unit, moments, stage_rows);

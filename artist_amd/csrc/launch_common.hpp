@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <atomic>
+#include <mutex>
+
 #include "../../include/artist_hip.h"
 
 namespace art {
@@ -18,6 +21,52 @@ extern thread_local int g_last_hip_error;
             return ART_ELAUNCH;                         \
         }                                               \
     } while (0)
+
+// Graph capture (include/artist_hip.h, Conventions): state that the library creates on first use - an allocation, a stream, an
+// event - is never created while the calling stream is being captured: an allocation made then fails AND invalidates the
+// capture.  Every such site asks this BEFORE it creates anything and, when the answer is yes, creates nothing; its entry point
+// returns ART_EUNSUPPORTED without having made a HIP call that could fail, so the capture stays valid.  Asked on the creating
+// path only: a call that finds its state pays nothing.
+static inline bool stream_is_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t rc = hipStreamIsCapturing(stream, &status);
+    if (rc != hipSuccess) {
+        (void)hipGetLastError();
+        return rc == hipErrorStreamCaptureImplicit;     // the legacy stream while a blocking stream captures: create nothing either
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+// The return code of an entry point whose first-use state (status word, work counters, window tables, side stream, part scratch)
+// could not be had: ART_EUNSUPPORTED when `stream` is being captured - nothing was created, no HIP call has failed, and the
+// caller runs the step once outside a capture first -, else the allocation failed.
+static inline int first_use_error(hipStream_t stream)
+{
+    if (stream_is_capturing(stream)) return ART_EUNSUPPORTED;
+    g_last_hip_error = (int)hipErrorOutOfMemory;
+    return ART_ELAUNCH;
+}
+
+// The dynamic-LDS limit of a kernel (hipFuncAttributeMaxDynamicSharedMemorySize) is an attribute of the function on a GPU, not
+// of a launch: it is raised when a launch asks for more than any launch of that kernel before it on this GPU, and left alone
+// otherwise - so a launch that repeats an earlier one (every launch of a captured step after its warm-up) makes no call besides
+// the launch itself.  `granted` is the caller's, one zero-initialised array per kernel instantiation.
+constexpr int kLdsGrantDevices = 64;
+struct LdsGrant { std::atomic<int> bytes[kLdsGrantDevices]; std::mutex lock; };
+static inline int grant_dynamic_lds(const void* kernel, LdsGrant& granted, size_t lds)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kLdsGrantDevices) {
+        ART_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return ART_OK;
+    }
+    if ((int)lds <= granted.bytes[dev].load(std::memory_order_acquire)) return ART_OK;
+    std::lock_guard<std::mutex> guard(granted.lock);
+    if ((int)lds <= granted.bytes[dev].load(std::memory_order_relaxed)) return ART_OK;
+    ART_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    granted.bytes[dev].store((int)lds, std::memory_order_release);
+    return ART_OK;
+}
 
 // Diagnostic knobs (launch geometry, A/B paths; results are the same bits or within the documented rounding for every value):
 // the library reads ARTIST_HIP_* variables ONLY when ARTIST_HIP_DEBUG=1 is set - a caller's environment cannot change what the

@@ -200,9 +200,10 @@ static inline bool interleaved_layout(const TraceArgs& a)
 // bit 0 when they meet a target index outside the tables (the heliostat is skipped), bit 1 when a heliostat has more
 // candidate rectangles inside its ray cone than the tables hold (art_blocking_filter; the surplus is not evaluated); the host reads it without a
 // synchronisation at the start of every trace call (a failure of an EARLIER launch then surfaces as ART_ETARGET / ART_ECANDIDATES) and,
-// synchronised, in art_async_status.
+// synchronised, in art_async_status.  `stream` is the caller's: the word is not allocated while that stream is being captured
+// (stream_is_capturing) - {nullptr, nullptr} then, which first_use_error() turns into the caller's return code.
 struct StatusWord { unsigned* host; unsigned* dev; };
-inline StatusWord status_word()
+inline StatusWord status_word(hipStream_t stream)
 {
     constexpr int kMaxDevices = 64;
     static StatusWord words[kMaxDevices] = {};
@@ -212,6 +213,7 @@ inline StatusWord status_word()
     std::lock_guard<std::mutex> guard(lock);
     if (words[dev].host == nullptr) {
         unsigned* h = nullptr; unsigned* d = nullptr;
+        if (stream_is_capturing(stream)) return {nullptr, nullptr};
         if (hipHostMalloc(reinterpret_cast<void**>(&h), 64, hipHostMallocMapped) != hipSuccess) return {nullptr, nullptr};
         *h = 0u;
         if (hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0) != hipSuccess) { (void)hipHostFree(h); return {nullptr, nullptr}; }

@@ -3079,6 +3079,7 @@ static unsigned* stream_work_counters(hipStream_t stream)
     std::lock_guard<std::mutex> guard(lock);
     for (const Entry& e : table)
         if (e.dev == dev && e.stream == stream) return e.base;
+    if (stream_is_capturing(stream)) return nullptr;        // no first use under capture, page at hand or not (first_use_error)
     if (page == nullptr || page_dev != dev || page_used == kPageEntries) {
         unsigned* fresh = nullptr;
         if (hipMalloc(reinterpret_cast<void**>(&fresh), 4096) != hipSuccess) return nullptr;
@@ -3095,7 +3096,11 @@ static unsigned* stream_work_counters(hipStream_t stream)
 // others) runs its two launches side by side: with the reference's tree the blocking launch has a few dozen items for 256
 // CUs and would otherwise hold the stream for the length of one item (0.5 ms forward, 1 ms backward at the metric size);
 // in exact mode the second launch fills the first one's tail.  One side stream + two events per host thread and device,
-// created on first use and kept; fork/join by events, so it also works under stream capture.  (Two host threads that drive
+// created on first use and kept; fork/join by events.  NOT while `stream` is being captured into a graph: begin() then
+// answers no, creates and records nothing, and the second launch follows the first one on `stream` - the same bits, one
+// branch.  (A forked capture would be joined from two host threads, the caller's and autograd's, and replaying a graph with
+// parallel branches depends on the number of hardware queues; a captured step is launch-bound, which is why it is captured, and
+// gains little from the overlap.  Of the split calls only the mixed tower is captured at all: blocking is refused.)  (Two host threads that drive
 // the SAME caller stream would share that stream's work counters: one stream, one thread at a time - as for any HIP stream.)
 struct SideStream {
     hipStream_t side = nullptr; hipEvent_t fork = nullptr, join = nullptr; int dev = -1; bool pending = false;
@@ -3104,6 +3109,7 @@ struct SideStream {
     bool begin(hipStream_t stream)
     {
         int d = 0;
+        if (stream_is_capturing(stream)) return false;
         if (hipGetDevice(&d) != hipSuccess) return false;
         if (dev != d) {
             if (dev >= 0) return false;                 // (never: side_stream() keeps one set per device)
@@ -3216,13 +3222,15 @@ static Window* stream_window_tables(hipStream_t stream)
     std::lock_guard<std::mutex> guard(lock);
     for (const Entry& e : table)
         if (e.dev == dev && e.stream == stream) return e.base;
+    if (stream_is_capturing(stream)) return nullptr;        // (launch_window_table reports it)
     Window* base = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&base), sizeof(Window) * 4 * kWindowTableItems) != hipSuccess) return nullptr;
     table.push_back({dev, stream, base});
     return base;
 }
 // Fills the table of launch `a` (role 0 ... 3) and points the launch at it; leaves a.win_table NULL when there is no table to be had.
-static void launch_window_table(TraceArgs& a, int role, int order, hipStream_t stream)
+// ART_OK either way, except for a stream that has no tables yet and is being captured: ART_EUNSUPPORTED, nothing allocated.
+static int launch_window_table(TraceArgs& a, int role, int order, hipStream_t stream)
 {
     a.win_table = nullptr;
     const int64_t items = host_item_count(a);
@@ -3232,14 +3240,15 @@ static void launch_window_table(TraceArgs& a, int role, int order, hipStream_t s
     // phase reads too, but as a prefetch of what the item traces next.  A field whose points fit the last-level cache (and whose
     // CUs see four items each, so that every prologue shows) is where the table pays.  (ARTIST_HIP_WINDOW_TABLE = 2 forces it: tests)
     const int mode = debug_env_int("ARTIST_HIP_WINDOW_TABLE", 1);
-    if (mode == 0 || items < 1 || items > kWindowTableItems || a.h_group > 1) return;
-    if (mode != 2 && (int64_t)a.H * a.P > 1500000) return;
+    if (mode == 0 || items < 1 || items > kWindowTableItems || a.h_group > 1) return ART_OK;
+    if (mode != 2 && (int64_t)a.H * a.P > 1500000) return ART_OK;
     Window* base = stream_window_tables(stream);
-    if (base == nullptr) return;
+    if (base == nullptr) return stream_is_capturing(stream) ? ART_EUNSUPPORTED : ART_OK;
     Window* tab = base + (int64_t)role * kWindowTableItems;
     if (interleaved_layout(a)) hipLaunchKernelGGL(window_table_kernel<true>, dim3((unsigned)items), dim3(256), 0, stream, a, tab, order);
     else hipLaunchKernelGGL(window_table_kernel<false>, dim3((unsigned)items), dim3(256), 0, stream, a, tab, order);
     a.win_table = tab;
+    return ART_OK;
 }
 
 // The queue's finer-grained end (lean kernels, whole samples per item): the heliostats of the LAST round of resident
@@ -3365,12 +3374,14 @@ static bool bwd_uses_lean_block(bool blocking, int64_t T, int64_t Tc)
     return blocking && debug_env_int("ARTIST_HIP_LEAN", 1) != 0 && T > 0 && Tc == 0 && debug_env_int("ARTIST_HIP_BLOCK_LEAN", 1) != 0;
 }
 
-// One instantiation of the windowed forward / backward kernel: its dynamic-LDS limit, then the launch.
+// One instantiation of the windowed forward / backward kernel: its dynamic-LDS limit (grant_dynamic_lds: set when it grows, not on
+// every launch), then the launch.
 template <bool IL, bool CY, bool BL, int LN>
 static int launch_fwd_lds(const FwdLaunch& launch, int64_t blocks, int threads, size_t lds, hipStream_t stream)
 {
-    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_fwd_lds_kernel<IL, CY, BL, LN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    static LdsGrant granted;
+    const int rc = grant_dynamic_lds(reinterpret_cast<const void*>(&trace_fwd_lds_kernel<IL, CY, BL, LN>), granted, lds);
+    if (rc != ART_OK) return rc;
     hipLaunchKernelGGL((trace_fwd_lds_kernel<IL, CY, BL, LN>), dim3((unsigned)blocks), dim3(threads), lds, stream, launch);
     return ART_OK;
 }
@@ -3378,8 +3389,9 @@ template <bool IL, bool AT, bool CY, bool BL, bool LN>
 static int launch_bwd_lds(const TraceArgs& a, const float* grad_flux, float4* go, float4* gn, float* prim_slabs, unsigned* work_counter,
                           int64_t blocks, int threads, size_t lds, hipStream_t stream)
 {
-    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_bwd_lds_kernel<IL, AT, CY, BL, LN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    static LdsGrant granted;
+    const int rc = grant_dynamic_lds(reinterpret_cast<const void*>(&trace_bwd_lds_kernel<IL, AT, CY, BL, LN>), granted, lds);
+    if (rc != ART_OK) return rc;
     hipLaunchKernelGGL((trace_bwd_lds_kernel<IL, AT, CY, BL, LN>), dim3((unsigned)blocks), dim3(threads), lds, stream, a, grad_flux, go, gn,
                        prim_slabs, work_counter);
     return ART_OK;
@@ -3415,7 +3427,8 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
                    plane_centers, plane_normals, plane_dims, cyl_centers, cyl_normals, cyl_axes, cyl_radii, cyl_heights,
                    cyl_opening, ray_magnitude, extinction, reflectivity, H, R, P, T, Tc, W, Hh, mode))
         return ART_EINVAL;
-    const StatusWord status = status_word();
+    const StatusWord status = status_word(stream);
+    if (status.host == nullptr && stream_is_capturing(stream)) return ART_EUNSUPPORTED;     // (first use under capture: see first_use_error)
     if (status.host != nullptr && (*status.host & 1u)) return ART_ETARGET;     // an earlier launch met a bad target index
     if (status.host != nullptr && (*status.host & 2u)) return ART_ECANDIDATES; // ... or more candidate rectangles than the tables hold
     if (status.host != nullptr && (*status.host & 4u)) return ART_EQUEUE;      // ... or a work counter that an aborted launch left behind
@@ -3423,6 +3436,7 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
     const bool blocking = prim_corners != nullptr;
     if (blocking) {
         if (!prim_spans || !prim_normals || !cand || !cand_count || Cmax < 1 || Cmax > (1 << 22)) return ART_EINVAL;
+        if (stream_is_capturing(stream)) return ART_EUNSUPPORTED;      // blocking is not captured into a graph (include/artist_hip.h)
         a.prim_corners = prim_corners; a.prim_spans = prim_spans; a.prim_normals = prim_normals;
         a.cand = cand; a.cand_count = cand_count; a.Cmax = (int)Cmax;
         set_cone(a, max_scatter_angle);
@@ -3431,10 +3445,7 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
     unsigned* counts = reinterpret_cast<unsigned*>(factors);
     // planar launch, cylinder launch, lean launch of a split call
     unsigned* const wc_base = stream_work_counters(stream);
-    if (wc_base == nullptr) {
-        g_last_hip_error = (int)hipErrorOutOfMemory;
-        return ART_ELAUNCH;
-    }
+    if (wc_base == nullptr) return first_use_error(stream);
     unsigned* work_counters[3] = {wc_base, wc_base + 1, wc_base + 2};
     if (debug_env_int("ARTIST_HIP_CORRUPT_COUNTER", 0) != 0)          // (tests: what an aborted launch leaves behind)
         ART_HIP(hipMemsetAsync(wc_base, 0x07, sizeof(unsigned), stream));
@@ -3481,7 +3492,7 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
             if (items_l > 2147483647LL - 65536) return ART_EINVAL;
             const int64_t blocks_l = (debug_env_int("ARTIST_HIP_PERSISTENT", 3) & 1) ? std::min<int64_t>(items_l, resident_workgroups()) : items_l;
             const size_t lds_l = ((size_t)al.tile_cap + 2) * sizeof(unsigned);
-            if (T > 0) launch_window_table(al, 1, -1, stream);          // (on `stream`, ahead of the side stream's start)
+            if (T > 0) { const int rc = launch_window_table(al, 1, -1, stream); if (rc != ART_OK) return rc; }   // (on `stream`, ahead of the side stream's start)
             const FwdLaunch launch = {al, flux, counts, work_counters[2]};
             const bool il_l = interleaved_layout(al);
             const int threads_l = cl.block;
@@ -3552,7 +3563,7 @@ extern "C" int art_trace_fwd(const float* origins, const float* normals, const f
             if (K > 1) { a.h_group = std::min(K, a.H); a.n_groups = (a.H + a.h_group - 1) / a.h_group; field_groups = true; }
         }
         if (lean && T > 0 && Tc == 0) set_queue_tail(a, 512);
-        if (lean && T > 0 && Tc == 0 && !field_groups) launch_window_table(a, 0, -1, stream);
+        if (lean && T > 0 && Tc == 0 && !field_groups) { const int rc = launch_window_table(a, 0, -1, stream); if (rc != ART_OK) return rc; }
         if (debug_env_int("ARTIST_HIP_PRINT_GEOMETRY", 0))
             fprintf(stderr, "art_trace_fwd: H %d P %d unit %d blocks/unit %d p_block %d n_pblocks %d r_chunk %d n_rchunks %d threads %d lean %d group %d tail %d x %d\n",
                     a.H, a.P, a.facet_points, a.blocks_per_facet, a.p_block, a.n_pblocks, a.r_chunk, a.n_rchunks, cfg.block, (int)lean,
@@ -3659,7 +3670,8 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
                    cyl_opening, ray_magnitude, extinction, reflectivity, H, R, P, T, Tc, W, Hh, mode))
         return ART_EINVAL;
     {
-        const StatusWord status = status_word();
+        const StatusWord status = status_word(stream);
+        if (status.host == nullptr && stream_is_capturing(stream)) return ART_EUNSUPPORTED;
         if (status.host != nullptr && (*status.host & 1u)) return ART_ETARGET;
         if (status.host != nullptr && (*status.host & 2u)) return ART_ECANDIDATES;
         if (status.host != nullptr && (*status.host & 4u)) return ART_EQUEUE;
@@ -3670,6 +3682,7 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
         if (!prim_spans || !prim_normals || !cand || !cand_count || Cmax < 1 || Cmax > (1 << 22) || N <= 0 ||
             !grad_prim_corners || !grad_prim_spans || !grad_prim_normals)
             return ART_EINVAL;
+        if (stream_is_capturing(stream)) return ART_EUNSUPPORTED;      // (as in art_trace_fwd)
         a.prim_corners = prim_corners; a.prim_spans = prim_spans; a.prim_normals = prim_normals;
         a.cand = cand; a.cand_count = cand_count; a.Cmax = (int)Cmax;
         set_cone(a, max_scatter_angle);
@@ -3745,10 +3758,10 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
                 const int64_t blocks_l = (debug_env_int("ARTIST_HIP_PERSISTENT", 3) & 2) ? std::min<int64_t>(items_l, resident_workgroups()) : items_l;
                 const size_t lds_l = ((size_t)al.tile_cap + 2) * sizeof(float) + perm_l;
                 unsigned* wc = stream_work_counters(stream);
-                if (wc == nullptr) { g_last_hip_error = (int)hipErrorOutOfMemory; return ART_ELAUNCH; }
+                if (wc == nullptr) return first_use_error(stream);
                 wc += 4;                                 // backward, lean launch of a split call
                 const int threads_l = lean_bwd_threads(al.p_block);
-                launch_window_table(al, 3, al.reverse_bwd != 0 ? 1 : 0, stream);
+                { const int rc = launch_window_table(al, 3, al.reverse_bwd != 0 ? 1 : 0, stream); if (rc != ART_OK) return rc; }
                 // submitted AFTER the blocking launch (see art_trace_fwd)
                 SideStream* ss = side_stream();
                 if (ss != nullptr && !ss->begin(stream)) ss = nullptr;
@@ -3762,7 +3775,7 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
             }
         }
         if (lean && a.n_rchunks == 1) set_queue_tail(a, 384);
-        if (lean && T > 0 && Tc == 0) launch_window_table(a, 2, a.reverse_bwd != 0 ? 1 : 0, stream);
+        if (lean && T > 0 && Tc == 0) { const int rc = launch_window_table(a, 2, a.reverse_bwd != 0 ? 1 : 0, stream); if (rc != ART_OK) return rc; }
         if (lean) cfg.block = lean_bwd_threads(a.p_block);       // (the geometry is fixed by now)
         const int64_t items = host_item_count(a);
         if (items > 2147483647LL - 65536) return ART_EINVAL;
@@ -3776,7 +3789,7 @@ extern "C" int art_trace_bwd(const float* origins, const float* normals, const f
         do {                                                                                                     \
             const int64_t blocks = ((CY && !LN && !kCylPersistentBwd) || (!CY && BL && !LN && !kBlockingPersistentBwd)) ? items : persistent_blocks; \
             unsigned* work_counter = stream_work_counters(stream);                                               \
-            if (work_counter == nullptr) { g_last_hip_error = (int)hipErrorOutOfMemory; return ART_ELAUNCH; }    \
+            if (work_counter == nullptr) return first_use_error(stream);                                         \
             work_counter += CY ? 6 : 5;                       /* backward: planar / cylinder launch */          \
             const int threads = std::min(cfg.block, CY ? kCylBwdThreads : (BL ? (LN ? kLeanBlockBwdThreads : kBlockingBwdThreads) : 1024)); \
             const int rc = launch_bwd_lds<IL, AT, CY, BL, LN>(a, grad_flux, go, gn, prim_slabs, work_counter, blocks, threads, lds, stream); \
@@ -3879,7 +3892,8 @@ extern "C" int art_per_target_sum(const float* bitmaps, const int32_t* target_id
 extern "C" int art_async_status(void* stream_, int clear)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const StatusWord status = status_word();
+    if (stream_is_capturing(stream)) return ART_EUNSUPPORTED;      // (a capture cannot wait: ask before it begins or after a replay)
+    const StatusWord status = status_word(stream);
     if (status.host == nullptr) { g_last_hip_error = (int)hipErrorOutOfMemory; return ART_ELAUNCH; }
     ART_HIP(hipStreamSynchronize(stream));
     const unsigned word = *status.host;

@@ -10,7 +10,7 @@ import weakref
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 _KNOT_CACHE: dict = {}
@@ -26,6 +26,8 @@ def _host_degrees(degrees: torch.Tensor) -> tuple[int, int]:
     entry = _DEGREE_CACHE.get(id(degrees))
     if entry is not None and entry[0]() is degrees and entry[1] == degrees._version:
         return entry[2]
+    if _lib.capturing():
+        raise _lib.first_use_under_capture("the host copy of the NURBS degrees")
     if len(_DEGREE_CACHE) > 256:
         _DEGREE_CACHE.clear()
     value = (int(degrees[0]), int(degrees[1]))
@@ -71,7 +73,8 @@ class NURBSSurfaces(torch.nn.Module):
             knot_vector = torch.zeros(n + degree + 1, device=device)
             knot_vector[degree:-degree] = torch.linspace(0, 1, n - degree + 1, device=device)
             knot_vector[-degree:] = 1
-            _KNOT_CACHE[key] = knot_vector
+            if not _lib.capturing():      # (built by captured ops it holds nothing until a replay: this surface's own, not kept)
+                _KNOT_CACHE[key] = knot_vector
         # expand() instead of repeat(): identical values, no H*F copies in HBM
         return knot_vector.unsqueeze(0).unsqueeze(0).expand(
             self.number_of_surfaces, self.number_of_facets_per_surface, -1)

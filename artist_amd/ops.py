@@ -94,9 +94,12 @@ def _converted(t: torch.Tensor, what: str, make):
     hit = _CONVERTED.get(key)
     if hit is not None:
         _CONVERTED.move_to_end(key)
+        _lib.keep_alive(hit[1])                     # (a captured step outlives this table's sixteen entries)
         return hit[1]
     out = make(t)
-    if out is not t and t.numel() <= (1 << 20):                                  # (nothing to keep when no copy was made)
+    # (a copy made while the stream is being captured holds nothing until the graph is replayed: it serves this call, whose
+    #  reader is captured behind it, and is not kept for an eager call to find)
+    if out is not t and t.numel() <= (1 << 20) and not _lib.capturing():       # (nothing to keep when no copy was made)
         _CONVERTED[key] = (t, out)
         while len(_CONVERTED) > 16:
             _CONVERTED.popitem(last=False)
@@ -164,8 +167,11 @@ def _accumulators(dev: torch.device, n: int) -> torch.Tensor:
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), _stream(dev))
     buf = _ACCUM.get(key)
     if buf is None or buf.numel() < n:
+        if _lib.capturing():     # a captured torch.zeros is a memset node: not zero until a replay, and zero is the kernels' invariant
+            raise _lib.first_use_under_capture("pixel accumulators of art_trace_fwd")
         buf = torch.zeros((n,), dtype=torch.int64, device=dev)
         _ACCUM[key] = buf
+    _lib.keep_alive(buf)                            # (_raise_status drops the table; a captured step keeps its buffer)
     return buf
 
 
@@ -249,6 +255,9 @@ def check_async_errors(device=None, clear: bool = True) -> None:
     incomplete rectangle list is also marked in the results themselves: zero bitmap and factors for a bad target index,
     NaN bitmap and factors for a candidate overflow."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if _lib.capturing():
+        raise _lib.ArtistHipError("check_async_errors waits for the device, which a stream under graph capture cannot do: "
+                                  "call it before the capture or after a replay")
     with torch.cuda.device(dev):
         # the status word is one per GPU (include/artist_hip.h): a kernel on ANY stream of this process may have set it,
         # so wait for the whole device, not only for the current stream
@@ -341,6 +350,9 @@ class TraceRays(torch.autograd.Function):
 
         blocking = prim_corners is not None
         shading = shade_corners is not None
+        if blocking and _lib.capturing():
+            raise _lib.ArtistHipError("blocking / shading under graph capture is not supported (the library refuses it with "
+                                      "ART_EUNSUPPORTED): trace with blocking eagerly, or capture the step with blocking_active=False")
         if (shading or not filter_active) and not blocking:
             raise ValueError("shading needs the blocking rectangles (prim_corners, prim_spans, prim_normals, owner)")
         if not shading and not filter_active:
@@ -396,7 +408,7 @@ class TraceRays(torch.autograd.Function):
                 prim_normals = torch.cat((prim_normals, _f32c(shade_normals)))
             block_tabs = (prim_corners, prim_spans, prim_normals, cand, cand_count)
             global _LAST_BLOCKING
-            _LAST_BLOCKING = (cand, cand_count)            # (diagnostics and tests: the last call's candidate lists, still on the device)
+            _LAST_BLOCKING = (cand, cand_count)            # (diagnostics and tests: the last call's candidate lists, still on the device; never a captured call's)
             block_ptrs = tuple(t.data_ptr() for t in block_tabs)
 
         flux = torch.empty((n_maps, height, width), dtype=torch.float32, device=dev)
@@ -420,6 +432,8 @@ class TraceRays(torch.autograd.Function):
         ctx.mark_non_differentiable(factors, flags)
         ctx.set_materialize_grads(False)            # no zero tensors (one fill kernel each) for outputs nobody differentiates
         if moments is not None:
+            # (kept under graph capture too: the entry serves this tensor object alone, sums and bitmaps are written by the same
+            #  captured launch, and the crop captured behind it must take the path it takes eagerly)
             _MOMENTS[flux.data_ptr()] = (weakref.ref(flux), moments)
             if len(_MOMENTS) > 64:
                 for key in [k for k, v in _MOMENTS.items() if v[0]() is None]:

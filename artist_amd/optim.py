@@ -36,6 +36,11 @@ class Adam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if _lib.capturing():
+            # art_adam_step takes the learning rate and the step number by value and forms the bias corrections on the host: a
+            # replay would repeat the step it was captured at
+            raise _lib.ArtistHipError("artist_amd.optim.Adam.step() cannot be captured into a graph (every replay would repeat "
+                                      "the same step number): keep it outside the graph - graph.replay(); optimizer.step()")
         loss = None
         if closure is not None:
             with torch.enable_grad():

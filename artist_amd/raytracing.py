@@ -22,7 +22,7 @@ import weakref
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .blocking import create_blocking_primitives_rectangles_by_index, create_shading_primitives
 from .sampling import DistortionsDataset, RestrictedDistributedSampler
 
@@ -51,6 +51,14 @@ def _version_of(t: torch.Tensor):
         return t._version
     except (RuntimeError, AttributeError):
         return None
+
+
+def _no_miss_under_capture(what: str) -> None:
+    """The per-tracer caches (checked targets, owner indices, scatter angle, local rows) are filled by host reads or from host
+    lists: none of that can happen while the stream is being captured into a graph, and a tensor made by a captured op holds
+    nothing for a later eager call to find.  A miss under capture is therefore an error that says what to do."""
+    if _lib.capturing():
+        raise _lib.first_use_under_capture(what)
 
 
 def target_area_counts(tower) -> tuple[int, int]:
@@ -180,7 +188,9 @@ class HeliostatRayTracer:
     def _local_rows(self, device):
         """(index tensor of the owned heliostat samples or None when this rank owns all, dist_u, dist_e of those rows)."""
         if self._local_cache is not None and self._local_cache[0] == device:
+            _lib.keep_alive(*self._local_cache[1:])
             return self._local_cache[1:]
+        _no_miss_under_capture("the rank's rows of the distortions")       # (index tensors built from host lists)
         ds = self.distortions_dataset
         du, de = ds.distortions_u, ds.distortions_e
         idx_list = self.distortions_sampler.rank_indices
@@ -290,6 +300,7 @@ class HeliostatRayTracer:
         version = _version_of(target_area_indices)
         if target_area_indices.numel() > 0 and not (version is not None and checked is not None and
                                                      checked[0]() is target_area_indices and checked[1] == version):
+            _no_miss_under_capture("the host check of target_area_indices")
             lo, hi = int(target_area_indices.min()), int(target_area_indices.max())
             if lo < 0 or hi >= sum(target_area_counts(tower)):
                 raise IndexError("target_area_indices out of range")
@@ -305,12 +316,14 @@ class HeliostatRayTracer:
         version = _version_of(active_heliostats_mask)
         key = (version, None if idx is None else id(idx), str(active_heliostats_mask.device))
         if version is None or cached is None or cached[0]() is not active_heliostats_mask or cached[1] != key:
+            _no_miss_under_capture("the rectangle index of each active heliostat (nonzero)")
             owner = torch.nonzero(active_heliostats_mask, as_tuple=True)[0]
             if idx is not None:
                 owner = owner.index_select(0, idx.to(owner.device))
             # (`idx` is kept alive by the entry, so its id cannot be handed to another tensor while the entry lives)
             self._owner_cache = cached = (weakref.ref(active_heliostats_mask), key, owner, idx)
         owner = cached[2]
+        _lib.keep_alive(owner)
         return corners, spans, normals, owner, self._max_scatter_angle(), self.lbvh_compat
 
     def _max_scatter_angle(self) -> float:
@@ -322,6 +335,7 @@ class HeliostatRayTracer:
         # valid for the SAME tensor objects at the same versions only: a bound that is too small would change results
         vu, ve = _version_of(u), _version_of(e)
         if vu is None or ve is None or cached is None or cached[0]() is not u or cached[1]() is not e or cached[2:] != (vu, ve):
+            _no_miss_under_capture("the largest scatter angle of the distortions")
             value = float(torch.maximum(u.abs().max(), e.abs().max()))
             self._scatter_angle_cache = ((weakref.ref(u), weakref.ref(e), vu, ve), value)
         return self._scatter_angle_cache[1]

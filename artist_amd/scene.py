@@ -331,6 +331,8 @@ class Sun:
                 (table is None or kept[4] == table._version):
             buf = kept[1]
         else:
+            if _lib.capturing():        # (a draw copies its rows from a host list, and a captured sample holds nothing to keep)
+                raise _lib.first_use_under_capture("the sun's distortion sample")
             self._cache = None          # the old sample goes first: at most one per sun is alive while the new one is drawn
             if table is None:
                 buf = ops.sample_distortions(rows, key[2], key[3], key[0], law[0], law[1], loc.device)

@@ -19,9 +19,18 @@
  *     counters in device memory (zero whenever no launch is using them: the launch's last fetch resets them, so
  *     there is no bound on the number of queued launches), per (host thread, GPU) one side stream + two events
  *     for the second launch of a split call (blocking on / mixed towers), per (GPU, stream) 40 KB of device memory
- *     for the part sums of art_flux_crop_pixel_loss_fwd/_bwd on small batches (allocated by the first such call
- *     on a stream - which must therefore not be made while the stream is being captured into a graph; the values
- *     are rewritten by every call that reads them); nothing else survives a call;
+ *     for the part sums of art_flux_crop_pixel_loss_fwd/_bwd on small batches (the values are rewritten by every
+ *     call that reads them), per (GPU, stream) 640 KB of window tables of the trace calls on small fields; nothing
+ *     else survives a call;
+ *   - graph capture: once a stream's state exists, the calls on it may be captured into a graph (hipStreamBeginCapture,
+ *     torch.cuda.graph) and replayed - the state's addresses are baked into the captured launches, so nothing else
+ *     may be launched on THAT stream for as long as the graph is replayed (launches that share a work counter are
+ *     ordered by their stream).  Nothing is ever created under capture: an entry point that finds its first-use state
+ *     missing while its stream is being captured returns ART_EUNSUPPORTED before it has made a HIP call that could
+ *     fail - the capture stays valid - and the caller makes the call once outside a capture first.  The second launch
+ *     of a split call is captured behind the first one on the caller's stream (no forked branch).  Not captured at
+ *     all: blocking / shading (art_blocking_filter and the trace calls with prim_corners != NULL return
+ *     ART_EUNSUPPORTED under capture) and art_async_status (it waits);
  *   - return 0 on success, a negative ART_E* code otherwise (never throws across the ABI);
  *     art_strerror() maps a code to text;
  *   - outputs are fully written by the callee (zero-filled first where they are accumulators).
@@ -108,9 +117,11 @@ int art_last_hip_error(void);
  *                     anyway; art_flux_crop_pixel_loss_fwd takes them.  Formed when Hh >= 4, Hh * W is even and
  *                     n_maps <= 65535; all-NaN otherwise (and for a heliostat whose blocking candidates overflowed).
  * Device memory: every buffer is the caller's, except 4 KB pages that the library allocates on first use and keeps
- * (work counters of its persistent workgroups: 32 bytes per stream that has made a trace call, see Conventions; the
- * first trace call on a stream must therefore not be made while that stream is being captured into a graph)
- * and 64 bytes of mapped host memory per GPU (the status word of art_async_status).
+ * (work counters of its persistent workgroups: 32 bytes per stream that has made a trace call, see Conventions),
+ * 640 KB of window tables per stream that has traced a small field, 40 KB of part scratch per stream that has called
+ * art_flux_crop_pixel_loss_fwd on a small batch, and 64 bytes of mapped host memory per GPU (the status word of
+ * art_async_status).  None of it is allocated while the calling stream is being captured: ART_EUNSUPPORTED then
+ * (Conventions, graph capture).
  * ------------------------------------------------------------------------------------------- */
 int art_trace_fwd(const float *origins, const float *normals, const float *incident,
                   const float *dist_u, const float *dist_e, int64_t dist_sh, int64_t dist_sr, int64_t dist_sp,
