@@ -11,6 +11,8 @@ backward, behind ARTIST's own call surface:
     artist_amd.RigidBody            <-> artist.field.kinematics_rigid_body.RigidBody (ideal + linear actuators)
     artist_amd.Scenario             <-> artist.scenario.scenario.Scenario (load_scenario_from_hdf5, index_mapping)
     artist_amd.optim.Adam           <-> torch.optim.Adam as the reconstructors use it (the epoch's optimiser step)
+    artist_amd.optim.AimPointOptimizer, artist_amd.training, artist_amd.flux.trapezoid_distribution
+                                    <-> artist.optim.AimPointOptimizer, artist.optim.training, artist.flux.bitmap.trapezoid_distribution
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer
                                     <-> artist.optim.SmoothnessRegularizer, IdealSurfaceRegularizer (the epoch's regularisers)
     artist_amd.SurfaceGenerator     <-> artist.scenario.surface_generator.SurfaceGenerator (+ fit_nurbs_batch: all facets at once)
@@ -22,10 +24,12 @@ All arithmetic runs in hand-written HIP kernels (``artist_amd/csrc``) reached th
 from ._lib import ArtistHipError, build, lib  # noqa: F401
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nurbs_control_points  # noqa: F401
 from .flux import (FocalSpotLoss, KLDivergenceLoss, PixelLoss, bitmap_coordinates_to_target_coordinates,  # noqa: F401
-                   crop_and_kl_loss, crop_and_pixel_loss, crop_flux_distributions_around_center, get_center_of_mass)
+                   crop_and_kl_loss, crop_and_pixel_loss, crop_flux_distributions_around_center, get_center_of_mass,
+                   trapezoid_distribution)
 from .kinematics import Actuators, RigidBody  # noqa: F401
 from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, perform_canting, trace_rays  # noqa: F401
-from . import optim  # noqa: F401
+from . import optim, training  # noqa: F401
+from .aim_point_optimizer import AimPointOptimizer  # noqa: F401
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer, surface_regularization_terms  # noqa: F401
 from .raytracing import HeliostatRayTracer  # noqa: F401
 from .scenario import Scenario, open_scenario_file  # noqa: F401

@@ -17,6 +17,25 @@ from . import _lib
 from .ops import _f32c, _require_cuda
 
 
+def trapezoid_distribution(total_width: int, slope_width: int, plateau_width: int,
+                           device: torch.device | None = None) -> torch.Tensor:
+    """A one-dimensional trapezoid ``[total_width]``, symmetric about the middle of the axis: 1 on a plateau of
+    ``plateau_width`` pixels, falling linearly to 0 over ``slope_width`` pixels on either side (artist/flux/bitmap.py:74-118).
+    A trapezoid wider than the axis has its slopes cut off, a narrower one is padded with zeros; ``slope_width == 0`` is the
+    hard rectangle.  The aim-point tutorial's target distribution is the outer product of two of these.
+
+    Plain torch (a ``[total_width]`` vector built once per run, not a hot path): works on the CPU and on the GPU.  ``device``
+    None is the GPU when there is one, like the reference's ``get_device``."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    total_width = int(total_width)
+    pixel = torch.arange(total_width, device=device)
+    beyond_plateau = torch.abs(pixel - (total_width - 1) / 2.0) - plateau_width / 2.0
+    if slope_width == 0:
+        return (beyond_plateau <= 0).to(dtype=torch.float32)
+    return 1 - (beyond_plateau / slope_width).clamp(min=0, max=1)
+
+
 def target_dimensions(solar_tower, target_area_indices: torch.Tensor) -> torch.Tensor:
     """``[B,2]`` (width, height) in metres of each bitmap's target area by GLOBAL index, planar first, cylindrical
     second: planar ``dimensions``, or ``radius * opening_angle`` and ``height`` (bitmap.py:183-216)."""

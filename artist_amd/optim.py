@@ -7,7 +7,7 @@ schedulers and ``zero_grad`` work as with torch's - and keeps torch's state layo
 The update rule is ``torch.optim.adam._single_tensor_adam`` in fp32; tests compare it with torch's over several steps.
 
 ``SmoothnessRegularizer`` and ``IdealSurfaceRegularizer`` (``artist_amd.regularizers``) are exported here as well, where the
-reference has them (``artist.optim``).
+reference has them (``artist.optim``), and so is ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``).
 """
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer
 
-__all__ = ["Adam", "SmoothnessRegularizer", "IdealSurfaceRegularizer"]
+__all__ = ["Adam", "AimPointOptimizer", "SmoothnessRegularizer", "IdealSurfaceRegularizer"]
 
 
 class Adam(torch.optim.Optimizer):
@@ -74,3 +74,6 @@ class Adam(torch.optim.Optimizer):
                           state["exp_avg_sq"].data_ptr(), p.numel(), float(group["lr"]), float(beta1), float(beta2),
                           float(group["eps"]), float(group["weight_decay"]), state["step"], 1 if group["maximize"] else 0, nu, nv)
         return loss
+
+
+from .aim_point_optimizer import AimPointOptimizer  # noqa: E402  (it steps with the Adam above)

@@ -414,6 +414,8 @@ class SolarTower:
             [t.number_of_target_areas for t in self.target_areas], device=device)
         names = [n for t in self.target_areas for n in t.names]
         self.target_name_to_index = {n: i for i, n in enumerate(names)}
+        # global index -> (the table it lives in, its row there) - artist/field/solar_tower.py:87-90
+        self.index_to_target_area = [(t, row) for t in self.target_areas for row in range(len(t.names))]
 
     @classmethod
     def from_hdf5(cls, config_file, device: torch.device | None = None) -> "SolarTower":
@@ -536,6 +538,8 @@ class HeliostatGroup:
 class HeliostatField:
     def __init__(self, heliostat_groups, device=None) -> None:
         self.heliostat_groups = list(heliostat_groups)
+        self.number_of_heliostats_per_group = torch.tensor([group.number_of_heliostats for group in self.heliostat_groups],
+                                                           device=device)                  # artist/field/heliostat_field.py:72-78
 
     @classmethod
     def from_hdf5(cls, config_file, prototype_surface=None, prototype_kinematics=None, prototype_actuators=None,
