@@ -13,6 +13,7 @@ backward, behind ARTIST's own call surface:
     artist_amd.optim.Adam           <-> torch.optim.Adam as the reconstructors use it (the epoch's optimiser step)
     artist_amd.optim.AimPointOptimizer, artist_amd.training, artist_amd.flux.trapezoid_distribution
                                     <-> artist.optim.AimPointOptimizer, artist.optim.training, artist.flux.bitmap.trapezoid_distribution
+    artist_amd.optim.SurfaceReconstructor <-> artist.optim.SurfaceReconstructor (CalibrationSamples: its data parser, in memory)
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer
                                     <-> artist.optim.SmoothnessRegularizer, IdealSurfaceRegularizer (the epoch's regularisers)
     artist_amd.SurfaceGenerator     <-> artist.scenario.surface_generator.SurfaceGenerator (+ fit_nurbs_batch: all facets at once)
@@ -30,6 +31,7 @@ from .kinematics import Actuators, RigidBody  # noqa: F401
 from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, perform_canting, trace_rays  # noqa: F401
 from . import optim, training  # noqa: F401
 from .aim_point_optimizer import AimPointOptimizer  # noqa: F401
+from .surface_reconstructor import CalibrationSamples, SurfaceReconstructor, flux_integral_constraint  # noqa: F401
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer, surface_regularization_terms  # noqa: F401
 from .raytracing import HeliostatRayTracer  # noqa: F401
 from .scenario import Scenario, open_scenario_file  # noqa: F401

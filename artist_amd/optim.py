@@ -7,7 +7,8 @@ schedulers and ``zero_grad`` work as with torch's - and keeps torch's state layo
 The update rule is ``torch.optim.adam._single_tensor_adam`` in fp32; tests compare it with torch's over several steps.
 
 ``SmoothnessRegularizer`` and ``IdealSurfaceRegularizer`` (``artist_amd.regularizers``) are exported here as well, where the
-reference has them (``artist.optim``), and so is ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``).
+reference has them (``artist.optim``), and so are ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``) and
+``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ import torch
 from . import _lib
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer
 
-__all__ = ["Adam", "AimPointOptimizer", "SmoothnessRegularizer", "IdealSurfaceRegularizer"]
+__all__ = ["Adam", "AimPointOptimizer", "SurfaceReconstructor", "SmoothnessRegularizer", "IdealSurfaceRegularizer"]
 
 
 class Adam(torch.optim.Optimizer):
@@ -77,3 +78,4 @@ class Adam(torch.optim.Optimizer):
 
 
 from .aim_point_optimizer import AimPointOptimizer  # noqa: E402  (it steps with the Adam above)
+from .surface_reconstructor import SurfaceReconstructor  # noqa: E402  (and so does this one)

@@ -559,6 +559,21 @@ class HeliostatField:
         return scenario.build_heliostat_field(heliostats, number_of_surface_points_per_facet,
                                               change_number_of_control_points_per_facet, dev)
 
+    def update_surfaces(self, device: torch.device | None = None) -> None:
+        """``surface_points`` / ``surface_normals`` of every group anew from its (detached) control points, on the square
+        evaluation grid the group was loaded with (artist/field/heliostat_field.py:437-503): what a reconstruction leaves
+        behind for the ray tracing after it."""
+        for group in self.heliostat_groups:
+            facets = int(group.number_of_facets_per_heliostat)
+            side = int(math.sqrt(group.surface_points.shape[1] / facets))
+            nets = group.nurbs_control_points.detach()
+            grid = create_nurbs_evaluation_grid(torch.tensor([side, side]), device=nets.device)
+            points, normals = NURBSSurfaces(group.nurbs_degrees, nets, device=nets.device).calculate_surface_points_and_normals(
+                grid[None, None].expand(int(group.number_of_heliostats), facets, -1, -1), group.canting, group.facet_translations)
+            heliostats = group.surface_points.shape[0]
+            group.surface_points = points.reshape(heliostats, -1, 4).detach()
+            group.surface_normals = normals.reshape(heliostats, -1, 4).detach()
+
 
 class Scenario:
     def __init__(self, power_plant_position, solar_tower, light_sources, heliostat_field) -> None:

@@ -1,0 +1,444 @@
+"""Surface reconstruction: learn every heliostat's NURBS control points from measured flux bitmaps of its calibration samples.
+Drop-in for ``artist.optim.SurfaceReconstructor`` (artist/optim/surface_reconstructor.py:50-1224): same constructor, same
+nested configuration, same ``reconstruct_surfaces()`` and return values, same histories, same loop.
+
+An epoch is assembled from what the package already has, all of it hand-written HIP on the hot path: NURBS
+evaluation (``art_nurbs_fwd/_bwd``), orientations from the rigid-body kinematics (``art_rigid_body_fwd``, no gradient),
+alignment (``art_align_fwd/_bwd``), the trace without blocking (``art_trace_fwd/_bwd``), the crop around the centre of mass
+(``art_flux_crop_fwd/_bwd``), the caller's loss on the cropped bitmaps (``art_flux_loss`` for ``PixelLoss`` /
+``KLDivergenceLoss``), the regularisers (``art_surface_regularizers_fwd/_bwd``) and the step (``art_adam_step``).  What is left
+on top are vectors per sample and per heliostat: the flux-integral constraint (:func:`flux_integral_constraint`, torch ops on
+whichever device its arguments live), the dynamic balancing and the mean.
+
+The samples of one heliostat share one control net.  Each active heliostat's surface is evaluated ONCE per epoch; its points
+and normals are repeated over the sample axis and aligned per sample.  Backwards, the per-sample gradients of the points are
+summed over that axis as ``[heliostats, samples, ...].sum(1)`` - a fixed order - before the one NURBS adjoint per heliostat:
+two runs give the same bits, and the NURBS work does not grow with the number of samples.
+
+Host reads: the loop reads the device ONCE per epoch - the epoch's six scalars, stacked (the stop test, early stopping and
+``ReduceLROnPlateau`` need the loss on the host); the multiplier and the reference integrals stay device tensors.  The group is
+activated for the training samples once and again after every validation, and one ray tracer per group serves all training
+epochs, another all validations: a tracer's distortions depend on the seed and the shapes only.
+"""
+from __future__ import annotations
+
+import logging
+from dataclasses import dataclass, field
+from functools import partial
+from typing import Any
+
+import torch
+
+from . import _lib, distributed, training
+from .flux import KLDivergenceLoss, PixelLoss, crop_flux_distributions_around_center
+from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid
+from .raytracing import HeliostatRayTracer
+from .regularizers import surface_regularization_terms
+from .training import reduce_loss_per_sample
+
+log = logging.getLogger(__name__)
+
+__all__ = ["SurfaceReconstructor", "CalibrationSamples", "GroupState", "EpochLoss", "flux_integral_constraint", "HISTORY_KEYS"]
+
+#: the per-epoch lists of a group's history, in the order the epoch's scalars are stacked; ``"test_loss"`` comes on top
+HISTORY_KEYS = ("total_loss", "flux_loss", "smoothness_regularizer", "ideal_regularizer", "flux_integral",
+                "flux_integral_constraint")
+
+_mean_over_samples = partial(torch.mean, dim=-1)
+
+
+def flux_integral_constraint(cropped_sums: torch.Tensor, reference: torch.Tensor, multiplier, rho: float, energy_tolerance: float,
+                             samples_per_heliostat: int, epsilon: float = 1e-12):
+    """The augmented-Lagrangian term that keeps a reconstruction from losing power (surface_reconstructor.py:593-654).
+
+    ``cropped_sums`` are the sums of the cropped predictions per sample, ``reference`` those of the first epoch.  A sample
+    violates by ``v = max(-energy_tolerance - (sum - reference) / (reference + eps), 0)``: by how much its relative loss of flux
+    exceeds the tolerance.  The violation of a heliostat is the mean over its samples, its term ``lambda v + rho / 2 v^2`` with
+    the heliostat's ``multiplier`` (a number or ``[heliostats]``).  Returns ``(term [heliostats], relative differences
+    [samples], violation [heliostats])``.  After the backward pass the multiplier moves to ``clamp(lambda + rho v, min=0)``.
+    Torch ops only, on the device of the arguments."""
+    relative = (cropped_sums - reference) / (reference + torch.tensor(epsilon))
+    violation = reduce_loss_per_sample(torch.clamp(-energy_tolerance - relative, min=0.0), samples_per_heliostat, _mean_over_samples)
+    return multiplier * violation + 0.5 * rho * violation ** 2, relative, violation
+
+
+class CalibrationSamples:
+    """Calibration samples held in memory, for callers without PAINT files: stands where the reference's
+    ``CalibrationDataParser`` stands, ``data = {"data_parser": CalibrationSamples(...), "heliostat_data_mapping": []}``.
+
+    ``samples`` are the six tensors of one heliostat group - measured flux ``[N, res_u, res_e]``, focal spots ``[N, 4]``,
+    incident ray directions ``[N, 4]``, motor positions ``[N, 2]``, the mask ``[heliostats]`` (samples per heliostat, the same
+    for all that have any; a heliostat's samples follow one another) and target area indices ``[N]`` - or a list of such
+    six-tuples, one per group in the field's order.  ``parse_data_for_reconstruction`` hands back the group's six, on ``device``."""
+
+    def __init__(self, samples) -> None:
+        self.samples = [tuple(samples)] if isinstance(samples[0], torch.Tensor) else [tuple(s) for s in samples]
+        for six in self.samples:
+            if len(six) != 6:
+                raise ValueError("a group's calibration samples are six tensors: measured flux, focal spots, incident ray "
+                                 "directions, motor positions, active heliostats mask, target area indices")
+
+    def parse_data_for_reconstruction(self, heliostat_data_mapping, heliostat_group, scenario, bitmap_resolution=None,
+                                      device: torch.device | None = None):
+        groups = scenario.heliostat_field.heliostat_groups
+        index = next(i for i, group in enumerate(groups) if group is heliostat_group)
+        return tuple(t.to(device) for t in self.samples[index])
+
+
+@dataclass
+class EpochLoss:
+    """One epoch's loss and its parts: ``total`` (the mean of ``total_per_heliostat``), the flux loss per sample and per
+    heliostat, the constraint's term, relative differences and violation, the balancing factors and the regularisers."""
+    total: torch.Tensor
+    total_per_heliostat: torch.Tensor
+    flux_loss_per_sample: torch.Tensor
+    flux_loss_per_heliostat: torch.Tensor
+    constraint: torch.Tensor
+    relative_differences: torch.Tensor
+    violation: torch.Tensor
+    alpha: torch.Tensor
+    smoothness: torch.Tensor
+    beta: torch.Tensor
+    ideal: torch.Tensor
+
+    def scalars(self) -> torch.Tensor:
+        """The six history values of the epoch (``HISTORY_KEYS``) as one ``[6]`` tensor on the device."""
+        with torch.no_grad():
+            return torch.stack([s.detach().reshape(()) for s in (
+                self.total, self.flux_loss_per_heliostat.mean(), (self.alpha * self.smoothness).mean(),
+                (self.beta * self.ideal).mean(), self.relative_differences.mean(), self.constraint.mean())])
+
+
+@dataclass
+class GroupState:
+    """What the epochs of one heliostat group share (``SurfaceReconstructor.prepare``)."""
+    index: int
+    group: Any
+    mask: torch.Tensor
+    split: training.TrainTestSplit
+    active_rows: torch.Tensor                   # group-local rows of the heliostats that have samples, [active] on the device
+    original_control_points: torch.Tensor       # their nets before the first step (frozen), [active, F, U, V, 3]
+    evaluation_points: torch.Tensor             # [active, F, M, 2] (expanded)
+    canting: torch.Tensor
+    facet_translations: torch.Tensor
+    optimizer: torch.optim.Optimizer
+    scheduler: Any
+    early_stopper: training.EarlyStopping
+    multiplier: torch.Tensor                    # lambda of the flux-integral constraint, [this rank's heliostats]
+    reference_integrals: torch.Tensor | None = None
+    activated: str | None = None                # "train" / "test": which samples the group is activated for
+    tracers: dict = field(default_factory=dict)
+    aim_points: dict = field(default_factory=dict)
+    rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
+
+
+def _gpu_device(device) -> torch.device:
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
+    device = torch.device("cpu") if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise _lib.ArtistHipError(f"SurfaceReconstructor runs on the GPU only (device {device}); there is no CPU fallback")
+    return device
+
+
+class SurfaceReconstructor:
+    """``artist.optim.SurfaceReconstructor``: see the module docstring; attributes as in the reference (:58-84).
+
+    ``prepare`` / ``predict_flux`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_surfaces`` runs per group, for
+    callers that step themselves."""
+
+    def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
+                 dni: float | None = None, number_of_surface_points: torch.Tensor = torch.tensor([50, 50]),
+                 bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), epsilon: float | None = 1e-12,
+                 plot_results: bool = False, device: torch.device | None = None) -> None:
+        if plot_results:
+            raise NotImplementedError("plot_results=True: plotting stays ARTIST's (artist/optim/surface_reconstructor.py)")
+        _gpu_device(device)
+        if ddp_setup["rank"] == 0:
+            log.info("Create a surface reconstructor.")
+        self.ddp_setup = ddp_setup
+        self.scenario = scenario
+        self.data = data
+        self.optimizer_dict = optimization_configuration["optimization"]
+        self.scheduler_dict = optimization_configuration["scheduler"]
+        self.constraint_dict = optimization_configuration["constraints"]
+        # (host copies: the evaluation grid and every tracer want the sizes on the host)
+        self.number_of_surface_points = torch.tensor([int(number_of_surface_points[0]), int(number_of_surface_points[1])])
+        self.dni = dni
+        self.bitmap_resolution = torch.tensor([int(bitmap_resolution[0]), int(bitmap_resolution[1])])
+        self.epsilon = epsilon
+        self.plot_results = False
+        self.validation_loss_pixel = PixelLoss()
+        self.validation_loss_kl_div = KLDivergenceLoss()
+
+    # ------------------------------------------------------------------------------------------
+    def prepare(self, heliostat_group_index: int, device: torch.device | None = None) -> GroupState | None:
+        """Everything before a group's first epoch (:343-474, 898-966): its calibration samples from
+        ``data["data_parser"].parse_data_for_reconstruction``, the train/test split, the evaluation grid, a frozen copy of the
+        nets of the heliostats that have samples, ``artist_amd.optim.Adam`` on ``heliostat_group.nurbs_control_points``, the
+        configured scheduler, early stopping and a zero multiplier.  None for a group without samples."""
+        from .optim import Adam
+        device = _gpu_device(device)
+        group = self.scenario.heliostat_field.heliostat_groups[heliostat_group_index]
+        flux_measured, focal_spots, incident, motor_positions, mask, targets = self.data["data_parser"].parse_data_for_reconstruction(
+            heliostat_data_mapping=self.data["heliostat_data_mapping"], heliostat_group=group, scenario=self.scenario,
+            bitmap_resolution=self.bitmap_resolution, device=device)
+        active_rows = torch.nonzero(mask > 0, as_tuple=True)[0]
+        if active_rows.numel() == 0:
+            return None
+        split = training.train_test_split(active_heliostats_mask=mask, flux_measured=flux_measured, focal_spots_measured=focal_spots,
+                                          incident_ray_directions=incident, motor_positions=motor_positions,
+                                          target_area_indices=targets, device=device)
+        active = int(active_rows.numel())
+        grid = create_nurbs_evaluation_grid(self.number_of_surface_points, device=device)
+        with torch.no_grad():
+            original = group.nurbs_control_points.index_select(0, active_rows).clone()
+        optimizer = Adam([group.nurbs_control_points.requires_grad_()], lr=float(self.optimizer_dict["initial_learning_rate"]))
+        scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=optimizer, parameters=self.scheduler_dict)
+        stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
+                                         patience=self.optimizer_dict["early_stopping_patience"],
+                                         min_improvement=self.optimizer_dict["early_stopping_delta"], relative=True)
+        state = GroupState(index=heliostat_group_index, group=group, mask=mask, split=split, active_rows=active_rows,
+                           original_control_points=original,
+                           evaluation_points=grid[None, None].expand(active, int(group.number_of_facets_per_heliostat), -1, -1),
+                           canting=group.canting.index_select(0, active_rows),
+                           facet_translations=group.facet_translations.index_select(0, active_rows),
+                           optimizer=optimizer, scheduler=scheduler, early_stopper=stopper, multiplier=torch.zeros((), device=device))
+        _, heliostat_rows = self._rank_rows(state, "train", device)
+        state.multiplier = torch.zeros(active if heliostat_rows is None else int(heliostat_rows.numel()), device=device)
+        return state
+
+    def _rank_rows(self, state: GroupState, kind: str, device):
+        """``(sample rows, heliostat rows)`` that this rank owns among the group's samples of ``kind`` and among its active
+        heliostats - index tensors on the device, or ``(None, None)`` when it owns all.  From the sampler's host list
+        (artist/raytracing/sampling.py:107-157): a heliostat's samples stay together."""
+        if kind not in state.rows:
+            split = state.split
+            samples = split.number_of_train_samples if kind == "train" else split.number_of_test_samples
+            active = int(state.active_rows.numel())
+            from .sampling import RestrictedDistributedSampler
+            owned = RestrictedDistributedSampler(active * samples, active, self.ddp_setup["heliostat_group_world_size"],
+                                                 self.ddp_setup["heliostat_group_rank"]).rank_indices
+            if owned == list(range(active * samples)):
+                state.rows[kind] = (None, None)
+            else:
+                state.rows[kind] = (torch.tensor(owned, dtype=torch.long, device=device),
+                                    torch.tensor([i // samples for i in owned[::samples]], dtype=torch.long, device=device))
+        return state.rows[kind]
+
+    def _cropped_flux(self, state: GroupState, kind: str, device) -> torch.Tensor:
+        """Control points -> cropped flux of this rank's samples of ``kind`` (:476-591 and :197-262): evaluate each active
+        heliostat once, repeat over its samples, align per sample, trace without blocking, crop around the centre of mass."""
+        group, split, tower = state.group, state.split, self.scenario.solar_tower
+        train = kind == "train"
+        mask = split.active_heliostats_mask_train if train else split.active_heliostats_mask_test
+        incident = split.incident_ray_directions_train if train else split.incident_ray_directions_test
+        targets = split.target_area_indices_train if train else split.target_area_indices_test
+        samples = split.number_of_train_samples if train else split.number_of_test_samples
+        if state.activated != kind:
+            with torch.no_grad():           # (the per-sample copies of the nets it makes are not what the gradient goes through)
+                group.activate_heliostats(active_heliostats_mask=mask, device=device)
+            state.activated = kind
+
+        nets = group.nurbs_control_points.index_select(0, state.active_rows)
+        points, normals = NURBSSurfaces(group.nurbs_degrees, nets, device=device).calculate_surface_points_and_normals(
+            state.evaluation_points, state.canting, state.facet_translations)
+        active, per_heliostat = points.shape[0], points.shape[1] * points.shape[2]
+        repeat = lambda t: t.reshape(active, 1, per_heliostat, 4).expand(-1, samples, -1, -1).reshape(  # noqa: E731
+            active * samples, per_heliostat, 4)              # backward: .sum(1) over the samples, a fixed order
+        group.active_surface_points, group.active_surface_normals = repeat(points), repeat(normals)
+        if kind not in state.aim_points:      # (the samples' targets do not change: a few small launches less per epoch)
+            state.aim_points[kind] = tower.get_centers_of_target_areas(target_area_indices=targets, device=device)
+        aim_points = state.aim_points[kind]
+        with torch.no_grad():               # nothing of the kinematics learns here
+            if getattr(group, "kinematics", None) is not None:
+                orientations = group.kinematics.incident_ray_directions_to_orientations(
+                    incident_ray_directions=incident, aim_points=aim_points, device=device)
+            else:
+                from .scene import ideal_orientations
+                orientations = ideal_orientations(group.active_positions, aim_points, incident)
+        group._align(orientations)
+
+        tracer = state.tracers.get(kind)
+        if tracer is None:
+            ddp = self.ddp_setup
+            tracer = state.tracers[kind] = HeliostatRayTracer(
+                scenario=self.scenario, heliostat_group=group, blocking_active=False, world_size=ddp["heliostat_group_world_size"],
+                rank=ddp["heliostat_group_rank"], batch_size=self.optimizer_dict["batch_size"],
+                random_seed=ddp["heliostat_group_rank"], bitmap_resolution=self.bitmap_resolution, dni=self.dni)
+        flux, _, _, _ = tracer.trace_rays(incident_ray_directions=incident, active_heliostats_mask=mask,
+                                          target_area_indices=targets, device=device)
+        return crop_flux_distributions_around_center(flux_distributions=flux, solar_tower=tower,
+                                                     target_area_indices=self._own(state, kind, targets, device), device=device)
+
+    def _own(self, state: GroupState, kind: str, per_sample: torch.Tensor, device) -> torch.Tensor:
+        """This rank's rows of a per-sample tensor of ``kind``; the tensor itself when the rank owns all (kept per tensor, so
+        that callers which remember a tensor object they have checked meet the same object every epoch)."""
+        sample_rows, _ = self._rank_rows(state, kind, device)
+        if sample_rows is None:
+            return per_sample
+        key = (kind, id(per_sample))
+        if key not in state.rows:
+            state.rows[key] = (per_sample, per_sample.index_select(0, sample_rows))
+        return state.rows[key][1]
+
+    def predict_flux(self, state: GroupState, device: torch.device | None = None) -> torch.Tensor:
+        """The cropped flux of this rank's training samples from the group's current control points,
+        ``[samples, res_u, res_e]``, inside the autograd graph (:476-591)."""
+        return self._cropped_flux(state, "train", _gpu_device(device))
+
+    def epoch_loss(self, state: GroupState, cropped_flux: torch.Tensor, loss_definition,
+                   device: torch.device | None = None) -> EpochLoss:
+        """An epoch's loss from its cropped flux (:984-1052): ``loss_definition`` against the measured bitmaps per sample,
+        the mean per heliostat, :func:`flux_integral_constraint` - the first call's cropped sums become the reference
+        integrals (``state.reference_integrals`` is None before) - and ``alpha S + beta I`` with the dynamic balancing of
+        ``artist_amd.surface_regularization_terms``.  The multiplier is left as it is: :meth:`update_multiplier`."""
+        device = _gpu_device(device)
+        split = state.split
+        samples = split.number_of_train_samples
+        per_sample = loss_definition(prediction=cropped_flux, ground_truth=self._own(state, "train", split.flux_measured_train, device),
+                                     target_area_indices=self._own(state, "train", split.target_area_indices_train, device),
+                                     reduction_dimensions=(1, 2), device=device)
+        per_heliostat = reduce_loss_per_sample(per_sample, samples, _mean_over_samples)
+        sums = cropped_flux.sum(dim=(1, 2))
+        if state.reference_integrals is None:
+            state.reference_integrals = sums.detach()
+        constraint, relative, violation = flux_integral_constraint(
+            sums, state.reference_integrals, state.multiplier, self.constraint_dict["rho_flux_integral"],
+            self.constraint_dict["energy_tolerance"], samples, self.epsilon)
+        _, heliostat_rows = self._rank_rows(state, "train", device)
+        rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
+        original = state.original_control_points if heliostat_rows is None else \
+            state.original_control_points.index_select(0, heliostat_rows)
+        alpha, smoothness, beta, ideal = surface_regularization_terms(
+            state.group.nurbs_control_points.index_select(0, rows), original, per_heliostat,
+            self.constraint_dict["weight_smoothness"], self.constraint_dict["weight_ideal_surface"], epsilon=self.epsilon)
+        total_per_heliostat = per_heliostat + constraint + alpha * smoothness + beta * ideal
+        return EpochLoss(total=total_per_heliostat.mean(), total_per_heliostat=total_per_heliostat, flux_loss_per_sample=per_sample,
+                         flux_loss_per_heliostat=per_heliostat, constraint=constraint, relative_differences=relative,
+                         violation=violation, alpha=alpha, smoothness=smoothness, beta=beta, ideal=ideal)
+
+    def update_multiplier(self, state: GroupState, violation: torch.Tensor) -> None:
+        """``lambda <- clamp(lambda + rho * violation, min=0)`` per heliostat, after the backward pass (:1056-1062)."""
+        with torch.no_grad():
+            state.multiplier = torch.clamp(state.multiplier + self.constraint_dict["rho_flux_integral"] * violation.detach(), min=0.0)
+
+    def validate(self, state: GroupState, device: torch.device | None = None) -> dict[str, torch.Tensor]:
+        """The group's test samples under the current control points (:157-303), without gradient: ``{"pixel_loss", "kl_div"}``,
+        each the mean over a heliostat's test samples, ``[this rank's heliostats]`` on the device.  Leaves the group activated
+        for the test samples; the next ``predict_flux`` activates it for training again."""
+        device = _gpu_device(device)
+        split = state.split
+        with torch.no_grad():
+            cropped = self._cropped_flux(state, "test", device)
+            measured = self._own(state, "test", split.flux_measured_test, device)
+            losses = {}
+            for key, loss in (("pixel_loss", self.validation_loss_pixel), ("kl_div", self.validation_loss_kl_div)):
+                losses[key] = reduce_loss_per_sample(loss(prediction=cropped, ground_truth=measured, reduction_dimensions=(1, 2)),
+                                                     split.number_of_test_samples, _mean_over_samples)
+        if log.isEnabledFor(logging.INFO):          # (two more reads of the device, only for a reader of the log)
+            log.info("pixel mean: %.5f, kl-div mean: %.5f", float(losses["pixel_loss"].mean()), float(losses["kl_div"].mean()))
+        return losses
+
+    # ------------------------------------------------------------------------------------------
+    def _synchronize_and_lock_gradients(self, parameter: torch.Tensor, device: torch.device | None = None) -> None:
+        """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
+        sub-world size.  Then the outer edges are locked (:749-788)."""
+        if parameter.grad is None:
+            return
+        ddp = self.ddp_setup
+        if ddp["is_nested"]:
+            distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
+            parameter.grad /= ddp["heliostat_group_world_size"]
+        parameter.grad = self.lock_control_points_on_outer_edges(gradients=parameter.grad, device=device)
+
+    def _synchronize_reconstruction_across_ranks(self, final_loss_per_heliostat: torch.Tensor, loss_history: list) -> list:
+        """Every group's control points from the first rank that owns the group, the final losses MIN-reduced (a heliostat
+        another rank reconstructed is ``inf`` here), the histories of all ranks gathered (:790-840).  Returns the histories
+        per rank; ``[loss_history]`` in a single process."""
+        ddp = self.ddp_setup
+        if not ddp["is_distributed"]:
+            return [loss_history]
+        with torch.no_grad():
+            for index, group in enumerate(self.scenario.heliostat_field.heliostat_groups):
+                torch.distributed.broadcast(group.nurbs_control_points.detach(), src=ddp["ranks_to_groups_mapping"][index][0])
+        torch.distributed.all_reduce(final_loss_per_heliostat, op=torch.distributed.ReduceOp.MIN)
+        histories: list = [[] for _ in range(ddp["world_size"])]
+        torch.distributed.all_gather_object(histories, loss_history)
+        log.info(f"Rank: {ddp['rank']}, synchronized after surface reconstruction.")
+        return histories
+
+    def reconstruct_surfaces(self, loss_definition, device: torch.device | None = None):
+        """Reconstruct the surfaces of the groups this rank owns (:842-1160).  Returns ``(final loss per heliostat of the
+        scenario on the CPU, +inf where a heliostat was not reconstructed; the histories: one list per rank, one entry per
+        group)``; an entry has the per-epoch float lists ``HISTORY_KEYS`` and ``"test_loss"``, the last validation's
+        ``{"pixel_loss", "kl_div"}`` per heliostat.  A group runs while its loss is above ``tolerance`` and
+        ``epoch <= max_epoch``, or until early stopping, which ends the group before that epoch's history entry.  Afterwards
+        the ranks are synchronised and the field's surface points follow the new control points (``update_surfaces``)."""
+        device = _gpu_device(device)
+        ddp = self.ddp_setup
+        rank = ddp["rank"]
+        if rank == 0:
+            log.info("Beginning surface reconstruction.")
+        groups = self.scenario.heliostat_field.heliostat_groups
+        sizes = [int(group.number_of_heliostats) for group in groups]
+        final_loss_per_heliostat = torch.full((sum(sizes),), torch.inf, device=device)
+        tolerance, max_epoch = float(self.optimizer_dict["tolerance"]), int(self.optimizer_dict["max_epoch"])
+        log_step = max_epoch if self.optimizer_dict["log_step"] == 0 else int(self.optimizer_dict["log_step"])
+        loss_history: list[dict] = []
+
+        for group_index in ddp["groups_to_ranks_mapping"][rank]:
+            state = self.prepare(group_index, device)
+            if state is None:                                        # a group without samples
+                continue
+            optimizer, scheduler = state.optimizer, state.scheduler
+            parameter = state.group.nurbs_control_points
+            history: dict = {key: [] for key in HISTORY_KEYS}
+            test_loss = None
+            loss_host = float("inf")
+            epoch = 0
+            while loss_host > tolerance and epoch <= max_epoch:
+                optimizer.zero_grad()
+                loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
+                loss.total.backward()
+                self.update_multiplier(state, loss.violation)
+                self._synchronize_and_lock_gradients(parameter, device)
+                optimizer.step()
+                # the epoch's scalars in ONE transfer, after the step has been queued
+                scalars = loss.scalars().tolist()
+                loss_host = scalars[0]
+                if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+                    scheduler.step(loss_host)
+                else:
+                    scheduler.step()
+                stop = state.early_stopper.step(loss_host)
+                if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
+                    log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
+                    test_loss = self.validate(state, device)
+                if stop:
+                    log.info(f"Early stopping at epoch {epoch}.")
+                    break
+                for key, value in zip(HISTORY_KEYS, scalars):
+                    history[key].append(value)
+                epoch += 1
+            history["test_loss"] = test_loss
+            loss_history.append(history)
+
+            _, heliostat_rows = self._rank_rows(state, "train", device)
+            rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
+            final_loss_per_heliostat[rows + sum(sizes[:group_index])] = loss.total_per_heliostat.detach()
+            log.info(f"Rank: {rank}, Surfaces reconstructed.")
+
+        histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history)
+        self.scenario.heliostat_field.update_surfaces(device=device)
+        return final_loss_per_heliostat.detach().cpu(), histories
+
+    @staticmethod
+    def lock_control_points_on_outer_edges(gradients: torch.Tensor, device: torch.device | None = None) -> torch.Tensor:
+        """A copy of ``gradients`` ``[heliostats, facets, U, V, 3]`` with the u and v components of every net's first and last
+        row and column set to zero (:1163-1224): the clamped knots make a surface end in its outer control points, so a
+        facet keeps its rectangular outline when those stay where they are; z stays free."""
+        with torch.no_grad():
+            locked = gradients.clone()
+            for edge in (locked[:, :, 0], locked[:, :, -1], locked[:, :, :, 0], locked[:, :, :, -1]):
+                edge[..., :2] = 0
+            return locked
