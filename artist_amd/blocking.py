@@ -23,6 +23,7 @@ import math
 import torch
 
 from . import _lib, ops
+from ._memo import Memo
 
 
 def _spans_and_normals(corners: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -33,7 +34,8 @@ def _spans_and_normals(corners: torch.Tensor) -> tuple[torch.Tensor, torch.Tenso
     return spans, normals
 
 
-_CORNER_INDEX: dict = {}
+# (one entry per number of surface points and device: no field here has sixteen)
+_CORNER_INDEX = Memo("the corner indices of the blocking rectangles", capacity=16)
 
 
 def create_blocking_primitives_rectangles_by_index(blocking_heliostats_active_surface_points: torch.Tensor,
@@ -48,12 +50,9 @@ def create_blocking_primitives_rectangles_by_index(blocking_heliostats_active_su
     pts = blocking_heliostats_active_surface_points
     P = pts.shape[1]
     side = math.sqrt(P / 4)
-    key = (P, pts.device)
-    index = _CORNER_INDEX.get(key)
-    if index is None:      # (a host list -> device tensor copy waits for the stream: once per shape, not once per trace call)
-        if _lib.capturing():
-            raise _lib.first_use_under_capture("the corner indices of the blocking rectangles")
-        index = _CORNER_INDEX[key] = torch.tensor([int(P / 2), int(side - 1), int((P / 2) - 1), int(P - side)], device=pts.device)
+    # (a host list -> device tensor copy waits for the stream: once per shape, not once per trace call)
+    index = _CORNER_INDEX.lookup((), lambda: torch.tensor([int(P / 2), int(side - 1), int((P / 2) - 1), int(P - side)],
+                                                          device=pts.device), key=(P, pts.device))
     corners = pts.index_select(1, index)
     spans, normals = _spans_and_normals(corners)
     return corners, spans, normals

@@ -15,6 +15,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import ops
 from .sampling import RestrictedDistributedSampler
 
 
@@ -34,16 +35,19 @@ def _exchanging(group=None) -> bool:
 
 def all_reduce_sum(tensor: torch.Tensor, group=None) -> torch.Tensor:
     """In-place SUM all-reduce; a no-op in a single-process run (same silent fallback as
-    artist/util/env.py:70-84)."""
+    artist/util/env.py:70-84).  The collective writes ``tensor`` without moving its version counter, so what was
+    remembered about a traced bitmap (``ops.bitmap_moments``) is forgotten first."""
     if _exchanging(group):
+        ops._MOMENTS.forget(tensor)
         dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=group)
     return tensor
 
 
 def all_reduce_sum_async(tensor: torch.Tensor, group=None):
     """Start an in-place SUM all-reduce and return a ``wait()``-able handle (None in a single-process run), so that
-    the 256 KB flux reduce travels over xGMI while the backward kernels run."""
+    the 256 KB flux reduce travels over xGMI while the backward kernels run.  Forgets like :func:`all_reduce_sum`."""
     if _exchanging(group):
+        ops._MOMENTS.forget(tensor)
         return dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=group, async_op=True)
     return None
 

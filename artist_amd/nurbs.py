@@ -6,33 +6,22 @@ not a chain of ATen ops.  Helper constructors follow ``artist/nurbs/utils.py``.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
-from . import _lib, ops
+from . import ops
+from ._memo import Memo
 
-
-_KNOT_CACHE: dict = {}
-_DEGREE_CACHE: dict = {}
+# (capacities that no workload here reaches: one knot vector per net size, degree and device; one degrees tensor per group)
+_KNOTS = Memo("the uniform knot vector of a net size", capacity=64, under_capture="serve")
+_DEGREES = Memo("the host copy of the NURBS degrees", capacity=256)
 
 
 def _host_degrees(degrees: torch.Tensor) -> tuple[int, int]:
     """``(p, q)`` as Python ints.  Reading a device tensor is a stream synchronisation, which would stop the host
-    from running ahead of the GPU once per epoch: the values are remembered for the SAME tensor object (weak
-    reference) at the same version - a new tensor, even at a recycled address, is read again."""
-    if degrees.device.type == "cpu":
-        return int(degrees[0]), int(degrees[1])
-    entry = _DEGREE_CACHE.get(id(degrees))
-    if entry is not None and entry[0]() is degrees and entry[1] == degrees._version:
-        return entry[2]
-    if _lib.capturing():
-        raise _lib.first_use_under_capture("the host copy of the NURBS degrees")
-    if len(_DEGREE_CACHE) > 256:
-        _DEGREE_CACHE.clear()
-    value = (int(degrees[0]), int(degrees[1]))
-    _DEGREE_CACHE[id(degrees)] = (weakref.ref(degrees), degrees._version, value)
-    return value
+    from running ahead of the GPU once per epoch: the values are remembered for the SAME tensor object at the same
+    version (artist_amd/_memo.py) - a new tensor, even at a recycled address, is read again."""
+    read = lambda: (int(degrees[0]), int(degrees[1]))       # noqa: E731
+    return read() if degrees.device.type == "cpu" else _DEGREES.lookup(degrees, read)
 
 
 class NURBSSurfaces(torch.nn.Module):
@@ -64,19 +53,16 @@ class NURBSSurfaces(torch.nn.Module):
         (artist/nurbs/surfaces.py:98-155)."""
         degree = self._degrees_host[direction]
         n = self.control_points.shape[2 + direction]
-        key = (n, degree, str(device))
-        knot_vector = _KNOT_CACHE.get(key)
-        if knot_vector is None:
-            # a reconstruction loop builds a NURBSSurfaces per epoch (surface_reconstructor.py:516-531): the knots
-            # depend on the sizes only, so they are built once per (size, degree, device) - five tiny kernels less
-            # per direction and epoch.  The cached tensor is shared: replace the attribute, never write into it.
+        def build() -> torch.Tensor:
             knot_vector = torch.zeros(n + degree + 1, device=device)
             knot_vector[degree:-degree] = torch.linspace(0, 1, n - degree + 1, device=device)
             knot_vector[-degree:] = 1
-            if not _lib.capturing():      # (built by captured ops it holds nothing until a replay: this surface's own, not kept)
-                _KNOT_CACHE[key] = knot_vector
+            return knot_vector
+        # a reconstruction loop builds a NURBSSurfaces per epoch (surface_reconstructor.py:516-531): the knots depend on
+        # the sizes only, so they are built once per (size, degree, device) - five tiny kernels less per direction and
+        # epoch.  The kept tensor is shared: replace the attribute, never write into it.
         # expand() instead of repeat(): identical values, no H*F copies in HBM
-        return knot_vector.unsqueeze(0).unsqueeze(0).expand(
+        return _KNOTS.lookup((), build, key=(n, degree, str(device))).unsqueeze(0).unsqueeze(0).expand(
             self.number_of_surfaces, self.number_of_facets_per_surface, -1)
 
     def _unique_counts(self) -> tuple[int, int]:

@@ -6,14 +6,11 @@ raise.
 """
 from __future__ import annotations
 
-import collections
 import math
-
-import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, _memo
 
 __all__ = ["trace_rays", "nurbs_surface_points_and_normals", "per_target_sum", "align_surfaces", "TraceRays",
            "NurbsEval", "AlignSurfaces", "check_async_errors", "record_launch_events",
@@ -78,36 +75,21 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 
 
 # Small per-call conversions that an optimisation loop repeats with the SAME tensors every epoch - the int32 copy of the
-# target indices, the [H,F,K] materialisation of an expanded knot vector - are kept, keyed by the source's address, shape,
-# strides and version counter (an in-place write makes a new entry).  Each is a 5 us kernel that a 1 ms epoch of a rank's
-# share of a field would pay several times over.  An entry holds the source tensor, so its address cannot be handed to another
-# tensor while the entry lives; sixteen entries of a few KB, the oldest goes first.
-_CONVERTED: "collections.OrderedDict" = collections.OrderedDict()
+# target indices, the [H,F,K] materialisation of an expanded knot vector - are kept (sixteen entries of a few KB).  Each is a
+# 5 us kernel that a 1 ms epoch of a rank's share of a field would pay several times over.
+_CONVERTED = _memo.Memo("a converted copy of an index or knot tensor", capacity=16, under_capture="serve", pin=True)
 
 
-def _converted(t: torch.Tensor, what: str, make):
-    try:
-        version = t._version
-    except (RuntimeError, AttributeError):          # inference-mode tensors have no version counter: no caching
-        return make(t)
-    key = (what, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, version, str(t.device))
-    hit = _CONVERTED.get(key)
-    if hit is not None:
-        _CONVERTED.move_to_end(key)
-        _lib.keep_alive(hit[1])                     # (a captured step outlives this table's sixteen entries)
-        return hit[1]
-    out = make(t)
-    # (a copy made while the stream is being captured holds nothing until the graph is replayed: it serves this call, whose
-    #  reader is captured behind it, and is not kept for an eager call to find)
-    if out is not t and t.numel() <= (1 << 20) and not _lib.capturing():       # (nothing to keep when no copy was made)
-        _CONVERTED[key] = (t, out)
-        while len(_CONVERTED) > 16:
-            _CONVERTED.popitem(last=False)
-    return out
+def _converted(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """``t`` as a contiguous ``dtype`` tensor: ``t`` itself when it is one already (nothing to keep when no copy is made)."""
+    if t.dtype == dtype and t.is_contiguous():
+        return t
+    make = lambda: t.to(dtype).contiguous()         # noqa: E731
+    return _CONVERTED.lookup(t, make, key=dtype) if t.numel() <= (1 << 20) else make()
 
 
 def _int32c(t: torch.Tensor) -> torch.Tensor:
-    return t if (t.dtype == torch.int32 and t.is_contiguous()) else _converted(t, "i32", lambda x: x.to(torch.int32).contiguous())
+    return _converted(t, torch.int32)
 
 
 def _dist_views(dist_u: torch.Tensor, dist_e: torch.Tensor, shape):
@@ -288,19 +270,21 @@ def _raise_status(code: int, what: str) -> None:
     _lib.check(code, what)
 
 
-# Centre-of-mass sums that came with a traced bitmap tensor: data pointer -> (weak reference to the tensor object, sums).  An
-# entry serves exactly the tensor OBJECT the trace returned, at the version it returned it with (an in-place edit, a copy or a
-# slice of the bitmaps is another tensor or another version: the crop then forms the sums itself).
-_MOMENTS: dict = {}
+# Centre-of-mass sums that came with a traced bitmap tensor.  An entry serves exactly the tensor OBJECT the trace returned, at
+# the version it returned it with (an in-place edit, a copy or a slice of the bitmaps is another tensor or another version: the
+# crop then forms the sums itself - the same bits).  64: more traced bitmap tensors than any caller here keeps alive at once.
+_MOMENTS = _memo.Memo("the centre-of-mass sums of traced bitmaps", capacity=64)
 
 
 def bitmap_moments(flux: torch.Tensor):
     """The sums ``art_trace_fwd`` left for ``flux`` (``[n_maps,4,3]`` float64) if ``flux`` is an untouched output of
-    :func:`trace_rays` / ``HeliostatRayTracer.trace_rays``, else None."""
-    entry = _MOMENTS.get(flux.data_ptr())
-    if entry is None or entry[0]() is not flux or flux._version != 0:
-        return None
-    return entry[1]
+    :func:`trace_rays` / ``HeliostatRayTracer.trace_rays``, else None.
+
+    "Untouched" is judged by the tensor's version counter, so a write that bypasses it - through ``.data``, by a raw kernel,
+    by ``torch.distributed`` called directly - is invisible and leaves stale sums behind.  The package's own in-place
+    helpers (``distributed.all_reduce_sum``, ``all_reduce_sum_async``, ``reduce_flux_per_target``) forget the sums of the
+    tensor they write; a caller that writes in such a way hands the crop a view (``flux[:]``: another object, no sums)."""
+    return _MOMENTS.get(flux)
 
 
 class TraceRays(torch.autograd.Function):
@@ -434,10 +418,7 @@ class TraceRays(torch.autograd.Function):
         if moments is not None:
             # (kept under graph capture too: the entry serves this tensor object alone, sums and bitmaps are written by the same
             #  captured launch, and the crop captured behind it must take the path it takes eagerly)
-            _MOMENTS[flux.data_ptr()] = (weakref.ref(flux), moments)
-            if len(_MOMENTS) > 64:
-                for key in [k for k, v in _MOMENTS.items() if v[0]() is None]:
-                    del _MOMENTS[key]
+            _MOMENTS.put(flux, moments)
         return flux, factors, flags
 
     @staticmethod
@@ -561,8 +542,8 @@ class NurbsEval(torch.autograd.Function):
         M = uv.shape[2]
         if uv.stride(3) != 1 or uv.stride(2) != 2 or (uv.data_ptr() % 8) != 0:
             uv = uv.contiguous()   # expanded (stride-0) heliostat/facet dims are passed through
-        ku = _converted(knots_u.expand(H, F, nu + p + 1), "knots", _f32c)
-        kv = _converted(knots_v.expand(H, F, nv + q + 1), "knots", _f32c)
+        ku = _converted(knots_u.expand(H, F, nu + p + 1), torch.float32)
+        kv = _converted(knots_v.expand(H, F, nv + q + 1), torch.float32)
         cant = None if canting is None else _f32c(canting)
         tr = None if canting is None else _f32c(translations.reshape(H, F, 4))
         points = torch.empty((H, F, M, 4), dtype=torch.float32, device=dev)

@@ -18,11 +18,10 @@ import os
 
 import logging
 
-import weakref
-
 import torch
 
 from . import _lib, ops
+from ._memo import Memo
 from .blocking import create_blocking_primitives_rectangles_by_index, create_shading_primitives
 from .sampling import DistortionsDataset, RestrictedDistributedSampler
 
@@ -41,24 +40,6 @@ def reflect(incident_ray_directions: torch.Tensor, reflection_surface_normals: t
             and nrm.dtype == torch.float32 and i.dtype == torch.float32 and not torch.is_grad_enabled()):
         return ops.reflect_directions(i[:, 0], nrm)
     return i - 2 * torch.sum(i * nrm, dim=-1, keepdim=True) * nrm
-
-
-def _version_of(t: torch.Tensor):
-    """``t._version`` or None where there is no version counter (inference-mode tensors): no caching then.  The per-call
-    caches of this module key on tensor identity + version, so index tensors and masks have to be changed with tracked
-    in-place ops (or replaced): a write through ``.data`` or by a raw kernel is invisible to them."""
-    try:
-        return t._version
-    except (RuntimeError, AttributeError):
-        return None
-
-
-def _no_miss_under_capture(what: str) -> None:
-    """The per-tracer caches (checked targets, owner indices, scatter angle, local rows) are filled by host reads or from host
-    lists: none of that can happen while the stream is being captured into a graph, and a tensor made by a captured op holds
-    nothing for a later eager call to find.  A miss under capture is therefore an error that says what to do."""
-    if _lib.capturing():
-        raise _lib.first_use_under_capture(what)
 
 
 def target_area_counts(tower) -> tuple[int, int]:
@@ -157,14 +138,11 @@ class HeliostatRayTracer:
             self.blocking_heliostat_surfaces = torch.cat(
                 [group.surface_points for group in self.scenario.heliostat_field.heliostat_groups])
             self.blocking_heliostat_surfaces_active = torch.cat(surfaces)
-            self._scatter_angle_cache = (None, 0.0)
         #: reproduce which rectangles the reference's LBVH can reach (see artist_amd/blocking.py); False = every
         #: rectangle whose box is hit, as ``lbvh_filter_blocking_planes`` documents
-        self._checked_targets = None
         self.lbvh_compat = True
         #: indices of the rectangles the last ``trace_rays`` call filtered (blocking only)
         self._filter_flags = self._filtered = None
-        self._owner_cache = None
         #: ``(shader_idx [H,S], shade_count [H])`` of the last ``trace_rays`` call (shading only), on the device
         self._shading = None
 
@@ -179,6 +157,11 @@ class HeliostatRayTracer:
         else:
             self.ray_magnitude = 1.0
         self._local_cache = None
+        # what a trace call learns from its arguments by a host read: once per tensor object and version (artist_amd/_memo.py),
+        # so index tensors and masks are changed with tracked in-place ops, or replaced
+        self._checked_targets = Memo("the host check of target_area_indices")
+        self._owner = Memo("the rectangle index of each active heliostat (nonzero)")
+        self._scatter_angle = Memo("the largest scatter angle of the distortions")
 
     # ------------------------------------------------------------------------------------------
     def get_sampler_indices(self) -> torch.Tensor:
@@ -190,7 +173,8 @@ class HeliostatRayTracer:
         if self._local_cache is not None and self._local_cache[0] == device:
             _lib.keep_alive(*self._local_cache[1:])
             return self._local_cache[1:]
-        _no_miss_under_capture("the rank's rows of the distortions")       # (index tensors built from host lists)
+        if _lib.capturing():                           # (index tensors built from host lists: not while the stream is captured)
+            raise _lib.first_use_under_capture("the rank's rows of the distortions")
         ds = self.distortions_dataset
         du, de = ds.distortions_u, ds.distortions_e
         idx_list = self.distortions_sampler.rank_indices
@@ -204,7 +188,6 @@ class HeliostatRayTracer:
             du, de = both[..., 0], both[..., 1]
         idx = None if owns_all else torch.tensor(idx_list, dtype=torch.long, device=device)
         self._local_cache = (device, idx, du, de)
-        self._owner_cache = None                       # (keyed on `idx`: rebuilt with it)
         return idx, du, de
 
     def _trace(self, incident_ray_directions, active_heliostats_mask, target_area_indices, ray_extinction_factor,
@@ -296,15 +279,13 @@ class HeliostatRayTracer:
         """The kernels index the target tables with these: validated on the host, once per tensor object and version
         (one host-device synchronisation, not one per epoch).  The C ABI checks them again on the device and reports
         ``ART_ETARGET`` instead of reading out of bounds (include/artist_hip.h)."""
-        checked = self._checked_targets
-        version = _version_of(target_area_indices)
-        if target_area_indices.numel() > 0 and not (version is not None and checked is not None and
-                                                     checked[0]() is target_area_indices and checked[1] == version):
-            _no_miss_under_capture("the host check of target_area_indices")
+        def check() -> bool:
             lo, hi = int(target_area_indices.min()), int(target_area_indices.max())
             if lo < 0 or hi >= sum(target_area_counts(tower)):
                 raise IndexError("target_area_indices out of range")
-            self._checked_targets = (weakref.ref(target_area_indices), version)
+            return True
+        if target_area_indices.numel() > 0:
+            self._checked_targets.lookup(target_area_indices, check)
 
     def _blocking_arguments(self, idx, active_heliostats_mask):
         """Rectangles of all heliostats (:291-301) + the rectangle index of each traced heliostat (:445-448)."""
@@ -312,33 +293,19 @@ class HeliostatRayTracer:
             return ()
         corners, spans, normals = create_blocking_primitives_rectangles_by_index(self.blocking_heliostat_surfaces_active)
         # rectangle index of each active heliostat: once per mask tensor object and version (nonzero() waits for the device)
-        cached = self._owner_cache
-        version = _version_of(active_heliostats_mask)
-        key = (version, None if idx is None else id(idx), str(active_heliostats_mask.device))
-        if version is None or cached is None or cached[0]() is not active_heliostats_mask or cached[1] != key:
-            _no_miss_under_capture("the rectangle index of each active heliostat (nonzero)")
+        def find() -> torch.Tensor:
             owner = torch.nonzero(active_heliostats_mask, as_tuple=True)[0]
-            if idx is not None:
-                owner = owner.index_select(0, idx.to(owner.device))
-            # (`idx` is kept alive by the entry, so its id cannot be handed to another tensor while the entry lives)
-            self._owner_cache = cached = (weakref.ref(active_heliostats_mask), key, owner, idx)
-        owner = cached[2]
-        _lib.keep_alive(owner)
+            return owner if idx is None else owner.index_select(0, idx.to(owner.device))
+        owner = self._owner.lookup((active_heliostats_mask, idx), find)
         return corners, spans, normals, owner, self._max_scatter_angle(), self.lbvh_compat
 
     def _max_scatter_angle(self) -> float:
         """Largest scatter angle of the distortion dataset: bounds every heliostat's ray cone for the blocking cull.
-        Computed once per dataset (one reduction + host read), again if a caller swaps the dataset's tensors."""
+        Computed once per dataset (one reduction + host read), again if a caller swaps or writes the dataset's tensors: a
+        bound that is too small would change results."""
         ds = self.distortions_dataset
         u, e = ds.distortions_u, ds.distortions_e
-        cached = self._scatter_angle_cache[0]
-        # valid for the SAME tensor objects at the same versions only: a bound that is too small would change results
-        vu, ve = _version_of(u), _version_of(e)
-        if vu is None or ve is None or cached is None or cached[0]() is not u or cached[1]() is not e or cached[2:] != (vu, ve):
-            _no_miss_under_capture("the largest scatter angle of the distortions")
-            value = float(torch.maximum(u.abs().max(), e.abs().max()))
-            self._scatter_angle_cache = ((weakref.ref(u), weakref.ref(e), vu, ve), value)
-        return self._scatter_angle_cache[1]
+        return self._scatter_angle.lookup((u, e), lambda: float(torch.maximum(u.abs().max(), e.abs().max())))
 
     def trace_rays_per_target(self, incident_ray_directions, active_heliostats_mask, target_area_indices,
                               ray_extinction_factor: float = 0.0, mirror_reflectivity: float = 0.935,

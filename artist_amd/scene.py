@@ -18,6 +18,7 @@ import math
 import numpy as np
 import torch
 
+from ._memo import Memo
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nurbs_control_points
 
 
@@ -196,7 +197,7 @@ class Sun:
             self.distribution = torch.distributions.MultivariateNormal(mean, cov)
         else:
             self.distribution = RadialSunShape(mean, _radial_table(params).to(mean.device))
-        self._law = None            # (distribution, tensor versions, host law) - see _host_law
+        self._law = Memo("the host copy of the sun's law")      # see _host_law
         self._cache = None          # (key, buffer, buffer version, table, table version) of the last "hip" draw
         self._sampler = None
         self.sampler = sampler
@@ -293,28 +294,25 @@ class Sun:
 
     def _host_law(self):
         """``(loc, scale_tril)`` of the current distribution as host floats (``(loc, None)`` for a radial sun, whose table stays
-        on the device).  Read from the device (one synchronisation) only when ``distribution`` is a new object or one of its
-        tensors was written since the last read."""
+        on the device).  Read from the device (one synchronisation) only when ``distribution`` has other tensors or one of
+        them was written since the last read (artist_amd/_memo.py)."""
         dist = self.distribution
         radial = isinstance(dist, RadialSunShape)
         loc, tril = dist.loc, None if radial else dist.scale_tril
-        versions = (loc._version, None if radial else tril._version)
-        kept = self._law
-        if kept is not None and kept[0] is dist and kept[1] == versions:
-            return kept[2]
-        if radial:
-            if tuple(loc.shape) != (2,):
-                raise ValueError(f"the centre of a radial sun must be 2 values, got loc {tuple(loc.shape)}")
-            law = (tuple(loc.detach().float().cpu().tolist()), None)
-            self._law = (dist, versions, law)
-            return law
-        if tuple(loc.shape) != (2,) or tuple(tril.shape) != (2, 2):
-            raise ValueError(f"the sun's distribution must be a single 2-D normal, got loc {tuple(loc.shape)}, "
-                             f"scale_tril {tuple(tril.shape)}")
-        v = torch.cat((loc.detach().reshape(-1), tril.detach().reshape(-1))).float().cpu().tolist()
-        law = ((v[0], v[1]), ((v[2], v[3]), (v[4], v[5])))
-        self._law = (dist, versions, law)
-        return law
+
+        def read():
+            if radial:
+                if tuple(loc.shape) != (2,):
+                    raise ValueError(f"the centre of a radial sun must be 2 values, got loc {tuple(loc.shape)}")
+                return tuple(loc.detach().float().cpu().tolist()), None
+            if tuple(loc.shape) != (2,) or tuple(tril.shape) != (2, 2):
+                raise ValueError(f"the sun's distribution must be a single 2-D normal, got loc {tuple(loc.shape)}, "
+                                 f"scale_tril {tuple(tril.shape)}")
+            v = torch.cat((loc.detach().reshape(-1), tril.detach().reshape(-1))).float().cpu().tolist()
+            return (v[0], v[1]), ((v[2], v[3]), (v[4], v[5]))
+        # (the law is a function of the two tensors and of the kind of distribution alone: another distribution object
+        #  around the same tensors has the same law)
+        return self._law.lookup((loc, tril), read, key=radial)
 
     def _hip_rows(self, rows, number_of_points: int, random_seed: int):
         from . import _lib, ops

@@ -30,6 +30,7 @@ from typing import Any
 import torch
 
 from . import _lib, distributed, training
+from ._memo import Memo
 from .flux import KLDivergenceLoss, PixelLoss, crop_flux_distributions_around_center
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid
 from .raytracing import HeliostatRayTracer
@@ -130,6 +131,8 @@ class GroupState:
     tracers: dict = field(default_factory=dict)
     aim_points: dict = field(default_factory=dict)
     rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
+    # this rank's rows of the per-sample tensors (_own): flux and targets, train and test - four, so eight are never reached
+    own: Memo = field(default_factory=lambda: Memo("this rank's rows of a per-sample tensor", capacity=8, under_capture="serve"))
 
 
 def _gpu_device(device) -> torch.device:
@@ -271,15 +274,12 @@ class SurfaceReconstructor:
                                                      target_area_indices=self._own(state, kind, targets, device), device=device)
 
     def _own(self, state: GroupState, kind: str, per_sample: torch.Tensor, device) -> torch.Tensor:
-        """This rank's rows of a per-sample tensor of ``kind``; the tensor itself when the rank owns all (kept per tensor, so
-        that callers which remember a tensor object they have checked meet the same object every epoch)."""
+        """This rank's rows of a per-sample tensor of ``kind``; the tensor itself when the rank owns all (kept per tensor object
+        and version, so that callers which remember a tensor object they have checked meet the same object every epoch)."""
         sample_rows, _ = self._rank_rows(state, kind, device)
         if sample_rows is None:
             return per_sample
-        key = (kind, id(per_sample))
-        if key not in state.rows:
-            state.rows[key] = (per_sample, per_sample.index_select(0, sample_rows))
-        return state.rows[key][1]
+        return state.own.lookup(per_sample, lambda: per_sample.index_select(0, sample_rows), key=kind)
 
     def predict_flux(self, state: GroupState, device: torch.device | None = None) -> torch.Tensor:
         """The cropped flux of this rank's training samples from the group's current control points,
