@@ -14,6 +14,8 @@ backward, behind ARTIST's own call surface:
     artist_amd.optim.AimPointOptimizer, artist_amd.training, artist_amd.flux.trapezoid_distribution
                                     <-> artist.optim.AimPointOptimizer, artist.optim.training, artist.flux.bitmap.trapezoid_distribution
     artist_amd.optim.SurfaceReconstructor <-> artist.optim.SurfaceReconstructor (CalibrationSamples: its data parser, in memory)
+    artist_amd.optim.KinematicsReconstructor, VectorLoss, AngleLoss, CosineSimilarityLoss
+                                    <-> artist.optim.KinematicsReconstructor ("raytracing" and "alignment"), artist.optim.loss
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer
                                     <-> artist.optim.SmoothnessRegularizer, IdealSurfaceRegularizer (the epoch's regularisers)
     artist_amd.SurfaceGenerator     <-> artist.scenario.surface_generator.SurfaceGenerator (+ fit_nurbs_batch: all facets at once)
@@ -32,6 +34,7 @@ from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_su
 from . import optim, training  # noqa: F401
 from .aim_point_optimizer import AimPointOptimizer  # noqa: F401
 from .surface_reconstructor import CalibrationSamples, SurfaceReconstructor, flux_integral_constraint  # noqa: F401
+from .kinematics_reconstructor import KinematicsReconstructor  # noqa: F401
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer, surface_regularization_terms  # noqa: F401
 from .raytracing import HeliostatRayTracer  # noqa: F401
 from .scenario import Scenario, open_scenario_file  # noqa: F401

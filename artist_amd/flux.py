@@ -278,8 +278,9 @@ def bitmap_coordinates_to_target_coordinates(bitmap_coordinates: torch.Tensor, b
         pi_ = tix.clamp(0, n_planar - 1)
         centers, dims = planar.centers.to(dev, dt)[pi_][:, :3], planar.dimensions.to(dev, dt)[pi_]
         e_local, u_local = (0.5 - e_norm) * dims[:, 0], (0.5 - u_norm) * dims[:, 1]
-        on_plane = centers + e_local[:, None] * torch.tensor([1.0, 0.0, 0.0], dtype=dt, device=dev) \
-            + u_local[:, None] * torch.tensor([0.0, 0.0, 1.0], dtype=dt, device=dev)
+        # east and up of the plane are the world's x and z (stacked: a unit vector built from a host list would be a copy to the
+        # device, which waits, in every call)
+        on_plane = centers + torch.stack((e_local, torch.zeros_like(e_local), u_local), dim=1)
         out3 = torch.where((tix < n_planar)[:, None], on_plane, out3)
     if n_cyl > 0:
         cyl = solar_tower.target_areas[1]

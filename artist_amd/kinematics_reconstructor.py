@@ -1,0 +1,378 @@
+"""Kinematics reconstruction: learn every heliostat's four rotation deviations from its calibration samples.
+Drop-in for ``artist.optim.KinematicsReconstructor`` (artist/optim/kinematics_reconstructor.py:29-1063): same constructor, same
+configuration, same two reconstruction methods, same ``reconstruct_kinematics()`` and return values, same loop.
+
+An epoch is assembled from what the package already has, all of it hand-written HIP on the hot path.  In the
+flux-driven mode (``"raytracing"``, :535-622): the rigid-body kinematics from the samples' motor positions
+(``art_rigid_body_fwd/_bwd``, mode 0), alignment (``art_align_fwd/_bwd``), the trace without blocking (``art_trace_fwd/_bwd``),
+the caller's loss on the bitmaps (``FocalSpotLoss``: ``art_flux_center_of_mass(_bwd)``), the median over a heliostat's samples,
+the mean over the heliostats and the step (``art_adam_step``).  In the alignment-driven mode (``"alignment"``, :421-533) nothing
+is traced: the predicted normal of a sample is the third column of its orientation, the measured one follows once from its focal
+spot, the heliostat's position and the incident ray direction, and the caller's loss (``artist_amd.losses``) compares the two -
+the mean over the samples, then over the heliostats.
+
+The samples of one heliostat share one row of deviations.  ``HeliostatGroup.activate_heliostats`` repeats the rows with
+``repeat_interleave``, whose backward is a scatter-add over a heliostat's samples.  Here the rows of the heliostats that have
+samples are taken once (``index_select``, unique rows) and expanded over the sample axis with a view, so the backward is
+``[heliostats, samples, 4].sum(1)`` - a fixed order: two runs give the same bits.
+
+Host reads: the loop reads the device ONCE per epoch - the loss, after the step has been queued (the stop test, early stopping
+and ``ReduceLROnPlateau`` need it on the host).  The group is activated for the training samples once and again after every
+validation; one ray tracer per group serves all training epochs, another - made the reference's way, seed 7 and a world of
+one - all validations.
+
+More than one rank has not run on a GPU: the collectives (``_synchronize_gradients_nested_ddp``,
+``_synchronize_reconstruction_across_ranks``) are tested with two gloo processes on CPU tensors.
+"""
+from __future__ import annotations
+
+import logging
+from dataclasses import dataclass, field
+from functools import partial
+from typing import Any
+
+import torch
+
+from . import _lib, distributed, training
+from ._memo import Memo
+from .flux import FocalSpotLoss, KLDivergenceLoss, PixelLoss
+from .raytracing import HeliostatRayTracer
+from .training import reduce_loss_per_sample
+
+log = logging.getLogger(__name__)
+
+__all__ = ["KinematicsReconstructor", "KinematicsGroupState", "KinematicsEpochLoss", "KINEMATICS_RECONSTRUCTION_RAYTRACING",
+           "KINEMATICS_RECONSTRUCTION_ALIGNMENT"]
+
+#: the two reconstruction methods (artist/util/constants.py)
+KINEMATICS_RECONSTRUCTION_RAYTRACING = "raytracing"
+KINEMATICS_RECONSTRUCTION_ALIGNMENT = "alignment"
+
+_mean_over_samples = partial(torch.mean, dim=-1)
+_median_over_samples = partial(torch.median, dim=1)
+
+
+@dataclass
+class KinematicsEpochLoss:
+    """One epoch's loss: ``total`` (the mean of ``per_heliostat``), the loss per sample and per heliostat of this rank, and
+    what the loss was taken of - the predicted flux ``[samples, res_u, res_e]`` or the predicted normals ``[samples, 4]``."""
+    total: torch.Tensor
+    per_heliostat: torch.Tensor
+    per_sample: torch.Tensor
+    prediction: torch.Tensor
+
+
+@dataclass
+class KinematicsGroupState:
+    """What the epochs of one heliostat group share (``KinematicsReconstructor.prepare``)."""
+    index: int
+    group: Any
+    mask: torch.Tensor
+    split: training.TrainTestSplit
+    active_rows: torch.Tensor                   # group-local rows of the heliostats that have samples, [active] on the device
+    optimizer: torch.optim.Optimizer
+    scheduler: Any
+    early_stopper: training.EarlyStopping
+    normals_measured: torch.Tensor | None = None    # alignment mode: of all samples, [samples, 4]
+    normals_measured_train: torch.Tensor | None = None
+    activated: str | None = None                # "train" / "test": which samples the group is activated for
+    surfaces: tuple | None = None               # the activated samples' surface points and normals before alignment
+    tracers: dict = field(default_factory=dict)
+    rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
+    # this rank's rows of the per-sample tensors (_own): flux and targets of the training samples
+    own: Memo = field(default_factory=lambda: Memo("this rank's rows of a per-sample tensor", capacity=8, under_capture="serve"))
+
+
+def _gpu_device(device) -> torch.device:
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
+    device = torch.device("cpu") if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise _lib.ArtistHipError(f"KinematicsReconstructor runs on the GPU only (device {device}); there is no CPU fallback")
+    return device
+
+
+class KinematicsReconstructor:
+    """``artist.optim.KinematicsReconstructor``: see the module docstring; attributes as in the reference (:38-60).
+
+    ``prepare`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_kinematics`` runs per group, for callers that step
+    themselves."""
+
+    def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
+                 dni: float | None = None, reconstruction_method: str = KINEMATICS_RECONSTRUCTION_RAYTRACING,
+                 bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), device: torch.device | None = None) -> None:
+        _gpu_device(device)
+        if ddp_setup["rank"] == 0:
+            log.info("Create a kinematics reconstructor.")
+        self.ddp_setup = ddp_setup
+        self.scenario = scenario
+        self.data = data
+        self.optimizer_dict = optimization_configuration["optimization"]
+        self.scheduler_dict = optimization_configuration["scheduler"]
+        self.dni = dni
+        self.bitmap_resolution = torch.tensor([int(bitmap_resolution[0]), int(bitmap_resolution[1])])   # (a host copy)
+        self.validation_loss_focal_spot = FocalSpotLoss(scenario=scenario)
+        self.validation_loss_pixel = PixelLoss()
+        self.validation_loss_kl_div = KLDivergenceLoss()
+        if reconstruction_method not in (KINEMATICS_RECONSTRUCTION_RAYTRACING, KINEMATICS_RECONSTRUCTION_ALIGNMENT):
+            raise ValueError(f"The kinematics reconstruction method '{reconstruction_method}' is unknown. "
+                             f"Please select another reconstruction method and try again!")
+        self.reconstruction_method = reconstruction_method
+
+    @property
+    def _flux_driven(self) -> bool:
+        return self.reconstruction_method == KINEMATICS_RECONSTRUCTION_RAYTRACING
+
+    # ------------------------------------------------------------------------------------------
+    def prepare(self, heliostat_group_index: int, device: torch.device | None = None) -> KinematicsGroupState | None:
+        """Everything before a group's first epoch (:332-419, 758-794, 937-964): its calibration samples from
+        ``data["data_parser"].parse_data_for_reconstruction``, the train/test split, in alignment mode the measured normals,
+        ``artist_amd.optim.Adam`` on ``kinematics.rotation_deviation_parameters``, the configured scheduler and early
+        stopping.  None for a group without samples."""
+        from .optim import Adam
+        device = _gpu_device(device)
+        group = self.scenario.heliostat_field.heliostat_groups[heliostat_group_index]
+        flux_measured, focal_spots, incident, motor_positions, mask, targets = self.data["data_parser"].parse_data_for_reconstruction(
+            heliostat_data_mapping=self.data["heliostat_data_mapping"], heliostat_group=group, scenario=self.scenario,
+            bitmap_resolution=self.bitmap_resolution, device=device)
+        active_rows = torch.nonzero(mask > 0, as_tuple=True)[0]
+        if active_rows.numel() == 0:
+            return None
+        split = training.train_test_split(active_heliostats_mask=mask, flux_measured=flux_measured, focal_spots_measured=focal_spots,
+                                          incident_ray_directions=incident, motor_positions=motor_positions,
+                                          target_area_indices=targets, device=device)
+        kinematics = group.kinematics
+        optimizer = Adam([kinematics.rotation_deviation_parameters.requires_grad_()],
+                         lr=float(self.optimizer_dict["initial_learning_rate_rotation_deviation"]))
+        scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=optimizer, parameters=self.scheduler_dict)
+        stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
+                                         patience=self.optimizer_dict["early_stopping_patience"],
+                                         min_improvement=self.optimizer_dict["early_stopping_delta"], relative=True)
+        state = KinematicsGroupState(index=heliostat_group_index, group=group, mask=mask, split=split, active_rows=active_rows,
+                                     optimizer=optimizer, scheduler=scheduler, early_stopper=stopper)
+        if not self._flux_driven:
+            state.normals_measured = self._compute_measured_normals(group, focal_spots, incident, mask, device)
+            state.normals_measured_train = state.normals_measured[split.train_indices.to(device)]
+        return state
+
+    @staticmethod
+    def _compute_measured_normals(heliostat_group, focal_spots_measured: torch.Tensor, incident_ray_directions: torch.Tensor,
+                                  active_heliostats_mask: torch.Tensor, device: torch.device | None = None) -> torch.Tensor:
+        """The normals the samples were measured under, ``[samples, 4]`` (:421-470): a mirror that sends the incident ray to
+        the measured focal spot has the normalised difference of the direction to the spot and the incident direction as its
+        normal.  On the device of the arguments."""
+        positions = heliostat_group.positions.repeat_interleave(active_heliostats_mask, dim=0)
+        to_focal_spot = torch.nn.functional.normalize(focal_spots_measured[:, :3] - positions[:, :3], p=2, dim=1)
+        normals = torch.nn.functional.normalize(to_focal_spot - incident_ray_directions[:, :3], dim=-1)
+        return torch.cat((normals, torch.zeros_like(normals[:, :1])), dim=1)
+
+    def _rank_rows(self, state: KinematicsGroupState, device):
+        """``(sample rows, heliostat rows)`` that this rank owns among the group's training samples and among its active
+        heliostats - index tensors on the device, or ``(None, None)`` when it owns all, as every rank does in alignment mode.
+        From the sampler's host list (artist/raytracing/sampling.py:107-157): a heliostat's samples stay together."""
+        if "train" not in state.rows:
+            samples = state.split.number_of_train_samples
+            active = int(state.active_rows.numel())
+            owned = list(range(active * samples))
+            if self._flux_driven:
+                from .sampling import RestrictedDistributedSampler
+                owned = RestrictedDistributedSampler(active * samples, active, self.ddp_setup["heliostat_group_world_size"],
+                                                     self.ddp_setup["heliostat_group_rank"]).rank_indices
+            if owned == list(range(active * samples)):
+                state.rows["train"] = (None, None)
+            else:
+                state.rows["train"] = (torch.tensor(owned, dtype=torch.long, device=device),
+                                       torch.tensor([i // samples for i in owned[::samples]], dtype=torch.long, device=device))
+        return state.rows["train"]
+
+    def _own(self, state: KinematicsGroupState, per_sample: torch.Tensor, device) -> torch.Tensor:
+        """This rank's rows of a per-sample tensor of the training samples; the tensor itself when the rank owns all."""
+        sample_rows, _ = self._rank_rows(state, device)
+        if sample_rows is None:
+            return per_sample
+        return state.own.lookup(per_sample, lambda: per_sample.index_select(0, sample_rows), key="train")
+
+    def _orientations(self, state: KinematicsGroupState, kind: str, device) -> torch.Tensor:
+        """Rotation deviations -> the orientations of the samples of ``kind``, ``[samples, 4, 4]`` (:506-514, 568-577).  The
+        group is activated for ``kind`` when it is not; the deviations of the heliostats that have samples are taken once and
+        expanded over the sample axis with a view."""
+        group, split = state.group, state.split
+        train = kind == "train"
+        mask = split.active_heliostats_mask_train if train else split.active_heliostats_mask_test
+        samples = split.number_of_train_samples if train else split.number_of_test_samples
+        if state.activated != kind:
+            with torch.no_grad():           # (the per-sample copies of the deviations it makes are not what the gradient goes through)
+                group.activate_heliostats(active_heliostats_mask=mask, device=device)
+            state.surfaces = (group.active_surface_points, group.active_surface_normals)
+            state.activated = kind
+        kinematics = group.kinematics
+        rows = kinematics.rotation_deviation_parameters.index_select(0, state.active_rows)
+        active = rows.shape[0]
+        kinematics.active_rotation_deviation_parameters = rows.reshape(active, 1, 4).expand(-1, samples, -1).reshape(
+            active * samples, 4)                                 # backward: .sum(1) over the samples, a fixed order
+        return kinematics.motor_positions_to_orientations(
+            motor_positions=split.motor_positions_train if train else split.motor_positions_test, device=device)
+
+    def _flux(self, state: KinematicsGroupState, kind: str, device) -> torch.Tensor:
+        """Rotation deviations -> the flux of the samples of ``kind`` (:568-597 and :214-239): orientations from the motor
+        positions, alignment, the trace without blocking.  Training: this rank's samples, the tracer seeded with the rank in
+        the group's sub-world; validation: all test samples on every rank, seed 7."""
+        group, split = state.group, state.split
+        train = kind == "train"
+        orientations = self._orientations(state, kind, device)
+        group.active_surface_points, group.active_surface_normals = state.surfaces      # (the last epoch left them aligned)
+        group._align(orientations)
+        tracer = state.tracers.get(kind)
+        if tracer is None:
+            ddp = self.ddp_setup
+            where = dict(world_size=ddp["heliostat_group_world_size"], rank=ddp["heliostat_group_rank"],
+                         random_seed=ddp["heliostat_group_rank"]) if train else {}
+            tracer = state.tracers[kind] = HeliostatRayTracer(
+                scenario=self.scenario, heliostat_group=group, blocking_active=False, batch_size=self.optimizer_dict["batch_size"],
+                bitmap_resolution=self.bitmap_resolution, dni=self.dni, **where)
+        flux, _, _, _ = tracer.trace_rays(
+            incident_ray_directions=split.incident_ray_directions_train if train else split.incident_ray_directions_test,
+            active_heliostats_mask=split.active_heliostats_mask_train if train else split.active_heliostats_mask_test,
+            target_area_indices=split.target_area_indices_train if train else split.target_area_indices_test, device=device)
+        return flux
+
+    def epoch_loss(self, state: KinematicsGroupState, loss_definition, device: torch.device | None = None) -> KinematicsEpochLoss:
+        """An epoch's loss from the group's current rotation deviations, inside the autograd graph.  Flux-driven (:535-622):
+        ``loss_definition`` on the predicted and the measured flux of this rank's training samples, the median over a
+        heliostat's samples.  Alignment-driven (:472-533): ``loss_definition(prediction, ground_truth)`` on the predicted and
+        the measured normals, the mean over a heliostat's samples.  The total is the mean over the heliostats."""
+        device = _gpu_device(device)
+        split = state.split
+        if self._flux_driven:
+            prediction = self._flux(state, "train", device)
+            per_sample = loss_definition(prediction=prediction, ground_truth=self._own(state, split.flux_measured_train, device),
+                                         target_area_indices=self._own(state, split.target_area_indices_train, device),
+                                         reduction_dimensions=(1, 2), device=device)
+            reduction = _median_over_samples
+        else:
+            # orientations @ (0, 0, 1, 0): the third column, as it stands
+            prediction = self._orientations(state, "train", device)[:, :, 2]
+            per_sample = loss_definition(prediction=prediction, ground_truth=state.normals_measured_train)
+            reduction = _mean_over_samples
+        per_heliostat = reduce_loss_per_sample(per_sample, split.number_of_train_samples, reduction)
+        return KinematicsEpochLoss(total=per_heliostat.mean(), per_heliostat=per_heliostat, per_sample=per_sample, prediction=prediction)
+
+    def validate(self, state: KinematicsGroupState, device: torch.device | None = None) -> dict[str, torch.Tensor]:
+        """The group's test samples under the current rotation deviations (:184-295), traced in both modes, without gradient:
+        ``{"pixel_loss", "kl_div", "focal_spot_loss"}``, each reduced over a heliostat's test samples - by the median in the
+        flux-driven mode, by the mean in the alignment-driven one - ``[active heliostats]`` on the device.  Leaves the group
+        activated for the test samples; the next ``epoch_loss`` activates it for training again."""
+        device = _gpu_device(device)
+        split = state.split
+        reduction = _median_over_samples if self._flux_driven else _mean_over_samples
+        with torch.no_grad():
+            flux = self._flux(state, "test", device)
+            measured = split.flux_measured_test
+            per_sample = {
+                "pixel_loss": self.validation_loss_pixel(prediction=flux, ground_truth=measured, reduction_dimensions=(1, 2)),
+                "kl_div": self.validation_loss_kl_div(prediction=flux, ground_truth=measured, reduction_dimensions=(1, 2)),
+                "focal_spot_loss": self.validation_loss_focal_spot(prediction=flux, ground_truth=measured,
+                                                                   target_area_indices=split.target_area_indices_test, device=device)}
+            losses = {key: reduce_loss_per_sample(value, split.number_of_test_samples, reduction) for key, value in per_sample.items()}
+        if log.isEnabledFor(logging.INFO):          # (three more reads of the device, only for a reader of the log)
+            log.info("test loss focal spot: %.5f, pixel: %.5f, kl-div: %.5f", float(losses["focal_spot_loss"].mean()),
+                     float(losses["pixel_loss"].mean()), float(losses["kl_div"].mean()))
+        return losses
+
+    # ------------------------------------------------------------------------------------------
+    def _synchronize_gradients_nested_ddp(self, optimizer: torch.optim.Optimizer) -> None:
+        """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
+        sub-world size (:624-648).  Flux-driven mode only."""
+        ddp = self.ddp_setup
+        if not ddp["is_nested"]:
+            return
+        for param_group in optimizer.param_groups:
+            for parameter in param_group["params"]:
+                if parameter.grad is not None:
+                    distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
+                    parameter.grad /= ddp["heliostat_group_world_size"]
+
+    def _synchronize_reconstruction_across_ranks(self, final_loss_per_heliostat: torch.Tensor, loss_history: list) -> list:
+        """Every group's rotation deviations and optimisable actuator parameters from the first rank that owns the group, the
+        final losses MIN-reduced (a heliostat another rank reconstructed is ``inf`` here), the histories of all ranks gathered
+        (:650-705).  Returns the histories per rank; ``[loss_history]`` in a single process."""
+        ddp = self.ddp_setup
+        if not ddp["is_distributed"]:
+            return [loss_history]
+        with torch.no_grad():
+            for index, group in enumerate(self.scenario.heliostat_field.heliostat_groups):
+                source = ddp["ranks_to_groups_mapping"][index][0]
+                torch.distributed.broadcast(group.kinematics.rotation_deviation_parameters.detach(), src=source)
+                torch.distributed.broadcast(group.kinematics.actuators.optimizable_parameters.detach(), src=source)
+        torch.distributed.all_reduce(final_loss_per_heliostat, op=torch.distributed.ReduceOp.MIN)
+        histories: list = [[] for _ in range(ddp["world_size"])]
+        torch.distributed.all_gather_object(histories, loss_history)
+        log.info(f"Rank: {ddp['rank']}, synchronized after kinematics reconstruction.")
+        return histories
+
+    def reconstruct_kinematics(self, loss_definition, device: torch.device | None = None):
+        """Reconstruct the rotation deviations of the groups this rank owns (:707-884 alignment-driven, :886-1063
+        flux-driven).  Returns ``(final loss per heliostat of the scenario on the CPU, +inf where a heliostat was not
+        reconstructed; the histories: one list per rank, one entry per group)``; an entry is ``{"total_loss": a float per epoch,
+        "test_loss": the last validation's {"pixel_loss", "kl_div", "focal_spot_loss"} per heliostat}``.  A group runs while its
+        loss is above ``tolerance`` and ``epoch <= max_epoch``, or until early stopping, which ends the group before that
+        epoch's history entry.  The flux-driven mode averages the gradients over a group's sub-world and synchronises the
+        ranks afterwards; the alignment-driven mode issues no collective, as in the reference, and returns this rank's
+        histories alone.  The parameters are detached at the end."""
+        device = _gpu_device(device)
+        ddp = self.ddp_setup
+        rank = ddp["rank"]
+        if rank == 0:
+            log.info("Beginning kinematics reconstruction with %s.", "ray tracing" if self._flux_driven else "alignment")
+        groups = self.scenario.heliostat_field.heliostat_groups
+        sizes = [int(group.number_of_heliostats) for group in groups]
+        final_loss_per_heliostat = torch.full((sum(sizes),), torch.inf, device=device)
+        tolerance, max_epoch = float(self.optimizer_dict["tolerance"]), int(self.optimizer_dict["max_epoch"])
+        log_step = max_epoch if self.optimizer_dict["log_step"] == 0 else int(self.optimizer_dict["log_step"])
+        loss_history: list[dict] = []
+
+        for group_index in ddp["groups_to_ranks_mapping"][rank]:
+            state = self.prepare(group_index, device)
+            if state is None:                                        # a group without samples
+                continue
+            optimizer, scheduler = state.optimizer, state.scheduler
+            parameter = optimizer.param_groups[0]["params"][0]
+            total_loss: list[float] = []
+            test_loss = None
+            loss_host = float("inf")
+            epoch = 0
+            while loss_host > tolerance and epoch <= max_epoch:
+                optimizer.zero_grad()
+                loss = self.epoch_loss(state, loss_definition, device)
+                loss.total.backward()
+                if self._flux_driven:
+                    self._synchronize_gradients_nested_ddp(optimizer)
+                else:
+                    # a sample whose normals are parallel has a non-finite gradient: it does not take part in the epoch
+                    parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
+                optimizer.step()
+                loss_host = loss.total.item()                        # the epoch's one read, after the step has been queued
+                if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+                    scheduler.step(loss_host)
+                else:
+                    scheduler.step()
+                stop = state.early_stopper.step(loss_host)
+                if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
+                    log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
+                    test_loss = self.validate(state, device)
+                if stop:
+                    log.info(f"Early stopping at epoch {epoch}.")
+                    break
+                total_loss.append(loss_host)
+                epoch += 1
+            loss_history.append({"total_loss": total_loss, "test_loss": test_loss})
+
+            _, heliostat_rows = self._rank_rows(state, device)
+            rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
+            final_loss_per_heliostat[rows + sum(sizes[:group_index])] = loss.per_heliostat.detach()
+            log.info(f"Rank: {rank}, Kinematics reconstructed.")
+
+        histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history) if self._flux_driven \
+            else [loss_history]
+        for group in groups:
+            group.kinematics.rotation_deviation_parameters = group.kinematics.rotation_deviation_parameters.detach()
+        return final_loss_per_heliostat.detach().cpu(), histories

@@ -7,17 +7,20 @@ schedulers and ``zero_grad`` work as with torch's - and keeps torch's state layo
 The update rule is ``torch.optim.adam._single_tensor_adam`` in fp32; tests compare it with torch's over several steps.
 
 ``SmoothnessRegularizer`` and ``IdealSurfaceRegularizer`` (``artist_amd.regularizers``) are exported here as well, where the
-reference has them (``artist.optim``), and so are ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``) and
-``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``).
+reference has them (``artist.optim``), and so are ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``),
+``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``), ``KinematicsReconstructor``
+(``artist_amd.kinematics_reconstructor``) and the losses on vectors it compares normals with (``artist_amd.losses``).
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
+from .losses import AngleLoss, CosineSimilarityLoss, VectorLoss
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer
 
-__all__ = ["Adam", "AimPointOptimizer", "SurfaceReconstructor", "SmoothnessRegularizer", "IdealSurfaceRegularizer"]
+__all__ = ["Adam", "AimPointOptimizer", "SurfaceReconstructor", "KinematicsReconstructor", "SmoothnessRegularizer",
+           "IdealSurfaceRegularizer", "VectorLoss", "AngleLoss", "CosineSimilarityLoss"]
 
 
 class Adam(torch.optim.Optimizer):
@@ -79,3 +82,4 @@ class Adam(torch.optim.Optimizer):
 
 from .aim_point_optimizer import AimPointOptimizer  # noqa: E402  (it steps with the Adam above)
 from .surface_reconstructor import SurfaceReconstructor  # noqa: E402  (and so does this one)
+from .kinematics_reconstructor import KinematicsReconstructor  # noqa: E402  (and this one)
