@@ -11,7 +11,8 @@
 // Backward = forward-mode differentiation: the same templated code runs on dual numbers (value, derivative), one
 // thread per (heliostat, parameter) seeds its parameter and contracts d(orientation) with dL/d(orientation).  17
 // parameters per heliostat (4 rotation deviations, 9 translation deviations, 2 x 2 optimisable actuator
-// parameters) x a few hundred flops: nothing next to the trace, and no hand-derived adjoint to get wrong.
+// parameters) x a few hundred flops: nothing next to the trace, and no hand-derived adjoint to get wrong.  One identity is
+// used instead of differentiated: angle -> motor position -> angle between two evaluations (see ChosenAngles).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,7 +41,8 @@ template <> struct Num<float> {
     static __device__ __forceinline__ float atan2_(float y, float x) { return atan2f(y, x); }
     static __device__ __forceinline__ float abs_(float x) { return fabsf(x); }
     static __device__ __forceinline__ float clamp_(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
-    static __device__ __forceinline__ float softplus100(float x) { const float b = 100.0f * x; return b > 20.0f ? x : logf(1.0f + expf(b)) / 100.0f; }
+    // F.softplus(beta=100) is log1p(exp(.)) in ATen: logf(1 + e) loses e's low bits where e is small (raw values below 0)
+    static __device__ __forceinline__ float softplus100(float x) { const float b = 100.0f * x; return b > 20.0f ? x : log1pf(expf(b)) / 100.0f; }
 };
 template <> struct Num<Dual> {
     static __device__ __forceinline__ Dual lift(float x) { return {x, 0.0f}; }
@@ -48,8 +50,10 @@ template <> struct Num<Dual> {
     static __device__ __forceinline__ Dual sin_(Dual x) { return {sinf(x.v), cosf(x.v) * x.d}; }
     static __device__ __forceinline__ Dual cos_(Dual x) { return {cosf(x.v), -sinf(x.v) * x.d}; }
     static __device__ __forceinline__ Dual sqrt_(Dual x) { const float s = sqrtf(x.v); return {s, x.d / (2.0f * s)}; }
-    static __device__ __forceinline__ Dual asin_(Dual x) { return {asinf(x.v), x.d / sqrtf(1.0f - x.v * x.v)}; }
-    static __device__ __forceinline__ Dual acos_(Dual x) { return {acosf(x.v), -x.d / sqrtf(1.0f - x.v * x.v)}; }
+    // a clamped argument carries derivative 0 and may sit on +-1 (1 - 1e-8 is 1 in fp32), where the slope is infinite: reverse
+    // mode (the reference) masks the infinite slope with the clamp's zero, forward mode must not form 0 * inf
+    static __device__ __forceinline__ Dual asin_(Dual x) { return {asinf(x.v), x.d == 0.0f ? 0.0f : x.d / sqrtf(1.0f - x.v * x.v)}; }
+    static __device__ __forceinline__ Dual acos_(Dual x) { return {acosf(x.v), x.d == 0.0f ? 0.0f : -x.d / sqrtf(1.0f - x.v * x.v)}; }
     static __device__ __forceinline__ Dual atan2_(Dual y, Dual x) { const float r2 = x.v * x.v + y.v * y.v; return {atan2f(y.v, x.v), (x.v * y.d - y.v * x.d) / r2}; }
     static __device__ __forceinline__ Dual abs_(Dual x) { return x.v < 0.0f ? Dual{-x.v, -x.d} : (x.v > 0.0f ? x : Dual{0.0f, 0.0f}); }
     // torch.clamp passes the gradient where min <= x <= max
@@ -59,7 +63,7 @@ template <> struct Num<Dual> {
         const float b = 100.0f * x.v;
         if (b > 20.0f) return x;
         const float e = expf(b);
-        return {logf(1.0f + e) / 100.0f, x.d * e / (1.0f + e)};
+        return {log1pf(e) / 100.0f, x.d * e / (1.0f + e)};
     }
 };
 
@@ -106,48 +110,70 @@ template <typename T> struct Params {          // everything of one heliostat th
 };
 
 // actuators_linear.py:206-233
-template <typename T> __device__ __forceinline__ T act_abs_angle(const Actuator<T>& a, T motor)
+// `cut` (optional): set when a clamp changed its argument, i.e. when motor position <-> angle is not invertible here
+template <typename T> __device__ __forceinline__ T clamp_cut(T x, float lo, float hi, bool* cut)
+{
+    if (cut && (Num<T>::val(x) < lo || Num<T>::val(x) > hi)) *cut = true;
+    return Num<T>::clamp_(x, lo, hi);
+}
+template <typename T> __device__ __forceinline__ T act_abs_angle(const Actuator<T>& a, T motor, bool* cut = nullptr)
 {
     using N = Num<T>;
     T stroke = motor / N::lift(a.increment) + a.init_stroke;
-    stroke = N::clamp_(stroke, fabsf(a.offset - a.pivot) + 1e-6f, a.offset + a.pivot - 1e-6f);
+    stroke = clamp_cut(stroke, fabsf(a.offset - a.pivot) + 1e-6f, a.offset + a.pivot - 1e-6f, cut);
     const T num = N::lift(a.offset * a.offset + a.pivot * a.pivot) - stroke * stroke;
-    return N::acos_(N::clamp_(num / N::lift(2.0f * a.offset * a.pivot), -1.0f + 1e-6f, 1.0f - 1e-6f));
+    return N::acos_(clamp_cut(num / N::lift(2.0f * a.offset * a.pivot), -1.0f + 1e-6f, 1.0f - 1e-6f, cut));
 }
 // ideal :87 / linear :260-291
-template <typename T> __device__ __forceinline__ T act_to_angle(const Actuator<T>& a, T motor)
+template <typename T> __device__ __forceinline__ T act_to_angle(const Actuator<T>& a, T motor, bool* cut = nullptr)
 {
     if (!a.linear) return motor;
-    const T delta = act_abs_angle(a, Num<T>::lift(0.0f)) - act_abs_angle(a, motor);
+    const T delta = act_abs_angle(a, Num<T>::lift(0.0f)) - act_abs_angle(a, motor, cut);
     return a.clockwise ? a.init_angle + delta : a.init_angle - delta;
 }
 // ideal :111 / linear :319-370
-template <typename T> __device__ __forceinline__ T act_to_motor(const Actuator<T>& a, T angle)
+template <typename T> __device__ __forceinline__ T act_to_motor(const Actuator<T>& a, T angle, bool* cut = nullptr)
 {
     using N = Num<T>;
     if (!a.linear) return angle;
     const T delta = a.clockwise ? angle - a.init_angle : a.init_angle - angle;
     const T init = act_abs_angle(a, N::lift(0.0f)) - delta;
-    const T c = N::clamp_(N::cos_(init), -1.0f + 1e-6f, 1.0f - 1e-6f);
+    // outside (0, pi) the law of cosines folds the angle back (acos(cos x) != x): not the identity either
+    if (cut && !(N::val(init) > 0.0f && N::val(init) < 3.14159265358979323846f)) *cut = true;
+    const T c = clamp_cut(N::cos_(init), -1.0f + 1e-6f, 1.0f - 1e-6f, cut);
     T stroke = N::sqrt_(N::lift(a.offset * a.offset + a.pivot * a.pivot) - N::lift(2.0f * a.offset * a.pivot) * c);
-    stroke = N::clamp_(stroke, fabsf(a.offset - a.pivot) + 1e-6f, a.offset + a.pivot - 1e-6f);
+    stroke = clamp_cut(stroke, fabsf(a.offset - a.pivot) + 1e-6f, a.offset + a.pivot - 1e-6f, cut);
     return (stroke - a.init_stroke) * N::lift(a.increment);
 }
 
 // kinematics_rigid_body.py:194-330
-template <typename T> __device__ __forceinline__ Mat4<T> kin_forward(const Params<T>& p, T motor0, T motor1)
+template <typename T> __device__ __forceinline__ Mat4<T> kin_forward_angles(const Params<T>& p, T th1, T th2)
 {
     using N = Num<T>;
-    const T th1 = act_to_angle(p.a1, motor0), th2 = act_to_angle(p.a2, motor1);
     Mat4<T> j1 = m_mul(m_mul(m_mul(m_rot_n(p.rot[0]), m_rot_u(p.rot[1])), m_trans(p.tr[0], p.tr[1], p.tr[2])), m_rot_e(th1));
     Mat4<T> j2 = m_mul(m_mul(m_mul(m_rot_e(p.rot[2]), m_rot_n(p.rot[3])), m_trans(p.tr[3], p.tr[4], p.tr[5])), m_rot_u(th2));
     Mat4<T> o = m_mul(m_trans(N::lift(p.pos[0]), N::lift(p.pos[1]), N::lift(p.pos[2])), j1);
     o = m_mul(o, j2);
     return m_mul(o, m_trans(p.tr[6], p.tr[7], p.tr[8]));
 }
+template <typename T> __device__ __forceinline__ Mat4<T> kin_forward(const Params<T>& p, T motor0, T motor1)
+{
+    return kin_forward_angles(p, act_to_angle(p.a1, motor0), act_to_angle(p.a2, motor1));
+}
+
+// The joint angles that the inverse kinematics chose, next to the motor positions it made of them (dual-number replay only).
+// Where no clamp cuts and nothing folds on the way angle -> motor position -> angle, that way is the identity in EVERY parameter (initial angle
+// and stroke length included: abs(f(x)) = x), so the next evaluation's joint angle carries the chosen angle's derivative as
+// it is.  Differentiating the round trip instead leaves abs0' - abs'(f(.)) f'(.) abs0', a few-ulp residue of terms that
+// cancel, where the derivative is 0.
+struct ChosenAngles {
+    Dual th[2];
+    bool whole[2];       // angle -> motor position: no clamp cut, no fold
+};
 
 // kinematics_rigid_body.py:331-507
-template <typename T> __device__ __forceinline__ void kin_inverse(const Params<T>& p, const T* normal, T& motor0, T& motor1)
+template <typename T> __device__ __forceinline__ void kin_inverse(const Params<T>& p, const T* normal, T& motor0, T& motor1,
+                                                                  ChosenAngles* chosen = nullptr)
 {
     using N = Num<T>;
     const float eps = 1e-8f, pi = 3.14159265358979323846f;
@@ -174,12 +200,19 @@ template <typename T> __device__ __forceinline__ void kin_inverse(const Params<T
         const T th = N::atan2_(vn * np[2] - vu * np[1], vn * np[1] + vu * np[2]);
         s1[k] = N::atan2_(N::sin_(th), N::cos_(th));
     }
-    const T a0 = act_to_motor(p.a1, s1[0]), b0 = act_to_motor(p.a2, s2[0]);
-    const T a1 = act_to_motor(p.a1, s1[1]), b1 = act_to_motor(p.a2, s2[1]);
+    bool cut[4] = {false, false, false, false};
+    const T a0 = act_to_motor(p.a1, s1[0], &cut[0]), b0 = act_to_motor(p.a2, s2[0], &cut[1]);
+    const T a1 = act_to_motor(p.a1, s1[1], &cut[2]), b1 = act_to_motor(p.a2, s2[1], &cut[3]);
     const bool ok = N::val(a0) >= p.a1.min_pos && N::val(a0) <= p.a1.max_pos && N::val(b0) >= p.a2.min_pos &&
                     N::val(b0) <= p.a2.max_pos;
     motor0 = ok ? a0 : a1;
     motor1 = ok ? b0 : b1;
+    if constexpr (sizeof(T) == sizeof(Dual)) {
+        if (chosen) {
+            chosen->th[0] = ok ? s1[0] : s1[1]; chosen->th[1] = ok ? s2[0] : s2[1];
+            chosen->whole[0] = !(ok ? cut[0] : cut[2]); chosen->whole[1] = !(ok ? cut[1] : cut[3]);
+        }
+    }
 }
 
 // desired concentrator normal for the current orientation (:594-611) and the loss of :613-616
@@ -310,12 +343,17 @@ __global__ __launch_bounds__(256) void rigid_body_bwd_kernel(KinArgs a, const fl
     Mat4<Dual> ori;
     if (a.mode == 1) {
         const int evals = *evals_in;
+        ChosenAngles chosen;
         for (int it = 0; it < evals; ++it) {
-            ori = kin_forward(p, m0, m1);
+            bool cut1 = false, cut2 = false;
+            Dual th1 = act_to_angle(p.a1, m0, &cut1), th2 = act_to_angle(p.a2, m1, &cut2);
+            if (it > 0 && p.a1.linear && chosen.whole[0] && !cut1) th1.d = chosen.th[0].d;
+            if (it > 0 && p.a2.linear && chosen.whole[1] && !cut2) th2.d = chosen.th[1].d;
+            ori = kin_forward_angles(p, th1, th2);
             if (it + 1 == evals) break;
             Dual dn[4], loss;
             desired_normal(ori, a.incident + 4 * h, a.aim + 4 * h, dn, loss);
-            kin_inverse(p, dn, m0, m1);
+            kin_inverse(p, dn, m0, m1, &chosen);
         }
     } else {
         m0 = {motor_in[2 * h], q == 17 ? 1.0f : 0.0f}; m1 = {motor_in[2 * h + 1], q == 18 ? 1.0f : 0.0f};

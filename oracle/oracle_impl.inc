@@ -816,10 +816,10 @@ static FN(mat4) FN(m_rot_u)(REAL x) { FN(mat4) r = FN(m_eye)(); REAL c = COS(x),
 static FN(mat4) FN(m_trans)(REAL e, REAL n, REAL u) { FN(mat4) r = FN(m_eye)(); r.m[3] = e; r.m[7] = n; r.m[11] = u; return r; }                            /* :215-262 */
 
 static inline REAL FN(clampr)(REAL x, REAL lo, REAL hi) { return x < lo ? lo : (x > hi ? hi : x); }
-static inline REAL FN(softplus100)(REAL x)   /* F.softplus(x, beta=100), threshold 20 */
+static inline REAL FN(softplus100)(REAL x)   /* F.softplus(x, beta=100), threshold 20: log1p(exp(.)), as ATen has it */
 {
     const REAL bx = (REAL)100 * x;
-    return bx > (REAL)20 ? x : LOG((REAL)1 + EXP(bx)) / (REAL)100;
+    return bx > (REAL)20 ? x : LOG1P(EXP(bx)) / (REAL)100;
 }
 
 /* one actuator column: non-optimisable rows (type, clockwise, min, max[, increment, offset, pivot radius]) and
