@@ -21,6 +21,11 @@ and ``ReduceLROnPlateau`` need it on the host).  The group is activated for the 
 validation; one ray tracer per group serves all training epochs, another - made the reference's way, seed 7 and a world of
 one - all validations.
 
+``epoch_graph=True`` ("The epoch as a graph"): per group the training step - ``epoch_loss`` and ``backward()`` -
+is captured once into an ``artist_amd.EpochGraph`` and replayed every epoch, in both modes; ``nan_to_num_`` on the gradient, the
+nested all-reduce, ``Adam.step()``, the one host read, the scheduler, early stopping, the history and every validation stay eager,
+in the same order.  The replayed epoch gives the eager epoch's bits.
+
 More than one rank has not run on a GPU: the collectives (``_synchronize_gradients_nested_ddp``,
 ``_synchronize_reconstruction_across_ranks``) are tested with two gloo processes on CPU tensors.
 """
@@ -37,6 +42,7 @@ from . import _lib, distributed, training
 from ._memo import Memo
 from .flux import FocalSpotLoss, KLDivergenceLoss, PixelLoss
 from .raytracing import HeliostatRayTracer
+from .surface_reconstructor import tensors_held_by
 from .training import reduce_loss_per_sample
 
 log = logging.getLogger(__name__)
@@ -81,6 +87,9 @@ class KinematicsGroupState:
     rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
     # this rank's rows of the per-sample tensors (_own): flux and targets of the training samples
     own: Memo = field(default_factory=lambda: Memo("this rank's rows of a per-sample tensor", capacity=8, under_capture="serve"))
+    # epoch_graph: the captured training step and what is kept alive for it
+    graph: Any = None
+    kept: list = field(default_factory=list)
 
 
 def _gpu_device(device) -> torch.device:
@@ -95,11 +104,19 @@ class KinematicsReconstructor:
     """``artist.optim.KinematicsReconstructor``: see the module docstring; attributes as in the reference (:38-60).
 
     ``prepare`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_kinematics`` runs per group, for callers that step
-    themselves."""
+    themselves.
+
+    ``epoch_graph`` (a public attribute, read when a group's loop starts): replay each group's training step from an
+    ``artist_amd.EpochGraph`` (:meth:`build_epoch_graph`) instead of running it eagerly, in both modes; the same bits, less host
+    time per epoch.  ``loss_definition`` must then not read the device (``.item()``, ``nonzero``, a host comparison): torch's
+    capture error propagates as it is, and there is no fall-back to the eager loop.  After a replay
+    ``heliostat_group.active_surface_points`` / ``active_surface_normals`` and the kinematics' ``active_*`` tables are whatever
+    the last eager call - the capture or a validation - left: a replay does not look at them."""
 
     def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
                  dni: float | None = None, reconstruction_method: str = KINEMATICS_RECONSTRUCTION_RAYTRACING,
-                 bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), device: torch.device | None = None) -> None:
+                 bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), device: torch.device | None = None,
+                 epoch_graph: bool = False) -> None:
         _gpu_device(device)
         if ddp_setup["rank"] == 0:
             log.info("Create a kinematics reconstructor.")
@@ -117,6 +134,7 @@ class KinematicsReconstructor:
             raise ValueError(f"The kinematics reconstruction method '{reconstruction_method}' is unknown. "
                              f"Please select another reconstruction method and try again!")
         self.reconstruction_method = reconstruction_method
+        self.epoch_graph = bool(epoch_graph)
 
     @property
     def _flux_driven(self) -> bool:
@@ -279,6 +297,46 @@ class KinematicsReconstructor:
         return losses
 
     # ------------------------------------------------------------------------------------------
+    def build_epoch_graph(self, state: KinematicsGroupState, loss_definition, device: torch.device | None = None):
+        """The group's training step - :meth:`epoch_loss` and ``backward()`` - as an ``artist_amd.EpochGraph`` (``state.graph``),
+        built after :meth:`prepare` and before the deviations' first use.  ``replay()`` leaves the gradient on
+        ``rotation_deviation_parameters`` and returns ``(total loss, loss per heliostat, loss per sample)``, detached, the bits
+        of the eager step.
+
+        The warm-up runs make what an eager first epoch makes - the activation for the training samples and, flux-driven, the
+        training tracer - and nothing else: no step of the optimiser, the scheduler or the early stopper.  The state keeps
+        every tensor that the captured step reads and that was made outside the capture (``state.kept``: the activation's
+        tables and the unaligned ``state.surfaces``, which ``activate_heliostats`` and a validation rebind and never write,
+        the measured normals, the rank's rows), so that a validation is not handed their memory.  The step is not activated
+        for training again after a validation.  :meth:`close_epoch_graph` ends it."""
+        from . import graphs
+        device = _gpu_device(device)
+        parameter = state.optimizer.param_groups[0]["params"][0]
+
+        def step():
+            loss = self.epoch_loss(state, loss_definition, device)
+            loss.total.backward()
+            return loss.total.detach(), loss.per_heliostat.detach(), loss.per_sample.detach()
+
+        try:
+            state.graph = graphs.EpochGraph(step, warmup=2, parameters=[parameter], device=device)
+        except BaseException:
+            self.close_epoch_graph(state)
+            raise
+        kinematics = state.group.kinematics
+        state.kept = tensors_held_by(state, state.group, kinematics, getattr(kinematics, "actuators", None))
+        return state.graph
+
+    def close_epoch_graph(self, state: KinematicsGroupState) -> None:
+        """Close ``state.graph`` and let go of what was kept for it.  No autograd graph that was built on the graph's stream
+        outlives it: what the capture left on the group and its kinematics is detached."""
+        if state.graph is not None:
+            state.graph.close()
+        state.graph, state.kept = None, []
+        group, kinematics = state.group, state.group.kinematics
+        group.active_surface_points, group.active_surface_normals = group.active_surface_points.detach(), group.active_surface_normals.detach()
+        kinematics.active_rotation_deviation_parameters = kinematics.active_rotation_deviation_parameters.detach()
+
     def _synchronize_gradients_nested_ddp(self, optimizer: torch.optim.Optimizer) -> None:
         """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
         sub-world size (:624-648).  Flux-driven mode only."""
@@ -340,35 +398,44 @@ class KinematicsReconstructor:
             test_loss = None
             loss_host = float("inf")
             epoch = 0
-            while loss_host > tolerance and epoch <= max_epoch:
-                optimizer.zero_grad()
-                loss = self.epoch_loss(state, loss_definition, device)
-                loss.total.backward()
-                if self._flux_driven:
-                    self._synchronize_gradients_nested_ddp(optimizer)
-                else:
-                    # a sample whose normals are parallel has a non-finite gradient: it does not take part in the epoch
-                    parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
-                optimizer.step()
-                loss_host = loss.total.item()                        # the epoch's one read, after the step has been queued
-                if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
-                    scheduler.step(loss_host)
-                else:
-                    scheduler.step()
-                stop = state.early_stopper.step(loss_host)
-                if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
-                    log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
-                    test_loss = self.validate(state, device)
-                if stop:
-                    log.info(f"Early stopping at epoch {epoch}.")
-                    break
-                total_loss.append(loss_host)
-                epoch += 1
-            loss_history.append({"total_loss": total_loss, "test_loss": test_loss})
+            graph = self.build_epoch_graph(state, loss_definition, device) if self.epoch_graph else None
+            try:
+                while loss_host > tolerance and epoch <= max_epoch:
+                    optimizer.zero_grad()
+                    if graph is None:
+                        loss = self.epoch_loss(state, loss_definition, device)
+                        loss.total.backward()
+                        total, per_heliostat = loss.total, loss.per_heliostat
+                    else:
+                        total, per_heliostat, _ = graph.replay()
+                    if self._flux_driven:
+                        self._synchronize_gradients_nested_ddp(optimizer)
+                    else:
+                        # a sample whose normals are parallel has a non-finite gradient: it does not take part in the epoch
+                        parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
+                    optimizer.step()
+                    loss_host = total.item()                             # the epoch's one read, after the step has been queued
+                    if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+                        scheduler.step(loss_host)
+                    else:
+                        scheduler.step()
+                    stop = state.early_stopper.step(loss_host)
+                    if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
+                        log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
+                        test_loss = self.validate(state, device)
+                    if stop:
+                        log.info(f"Early stopping at epoch {epoch}.")
+                        break
+                    total_loss.append(loss_host)
+                    epoch += 1
+                loss_history.append({"total_loss": total_loss, "test_loss": test_loss})
 
-            _, heliostat_rows = self._rank_rows(state, device)
-            rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
-            final_loss_per_heliostat[rows + sum(sizes[:group_index])] = loss.per_heliostat.detach()
+                _, heliostat_rows = self._rank_rows(state, device)
+                rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
+                final_loss_per_heliostat[rows + sum(sizes[:group_index])] = per_heliostat.detach()          # (the last replay's)
+            finally:
+                if graph is not None:
+                    self.close_epoch_graph(state)
             log.info(f"Rank: {rank}, Kinematics reconstructed.")
 
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history) if self._flux_driven \

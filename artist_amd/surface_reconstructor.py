@@ -19,6 +19,11 @@ Host reads: the loop reads the device ONCE per epoch - the epoch's six scalars, 
 ``ReduceLROnPlateau`` need the loss on the host); the multiplier and the reference integrals stay device tensors.  The group is
 activated for the training samples once and again after every validation, and one ray tracer per group serves all training
 epochs, another all validations: a tracer's distortions depend on the seed and the shapes only.
+
+``epoch_graph=True`` ("The epoch as a graph"): per group the training step - ``predict_flux``, ``epoch_loss``,
+``backward()`` - is captured once into an ``artist_amd.EpochGraph`` and replayed every epoch; the multiplier update, the nested
+all-reduce, the edge lock, ``Adam.step()``, the one host transfer, the scheduler, early stopping, the history and every
+validation stay eager, in the same order.  The replayed epoch gives the eager epoch's bits.
 """
 from __future__ import annotations
 
@@ -39,7 +44,8 @@ from .training import reduce_loss_per_sample
 
 log = logging.getLogger(__name__)
 
-__all__ = ["SurfaceReconstructor", "CalibrationSamples", "GroupState", "EpochLoss", "flux_integral_constraint", "HISTORY_KEYS"]
+__all__ = ["SurfaceReconstructor", "CalibrationSamples", "GroupState", "EpochLoss", "flux_integral_constraint", "HISTORY_KEYS",
+           "tensors_held_by"]
 
 #: the per-epoch lists of a group's history, in the order the epoch's scalars are stacked; ``"test_loss"`` comes on top
 HISTORY_KEYS = ("total_loss", "flux_loss", "smoothness_regularizer", "ideal_regularizer", "flux_integral",
@@ -133,6 +139,26 @@ class GroupState:
     rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
     # this rank's rows of the per-sample tensors (_own): flux and targets, train and test - four, so eight are never reached
     own: Memo = field(default_factory=lambda: Memo("this rank's rows of a per-sample tensor", capacity=8, under_capture="serve"))
+    # epoch_graph: the captured training step, whether the state a captured step reads must stay where it is, what is kept alive
+    # for the graph, and the ideal mount's orientations per kind (constants; their geometry copies from the host in every call)
+    graph: Any = None
+    static: bool = False
+    kept: list = field(default_factory=list)
+    orientations: dict = field(default_factory=dict)
+
+
+def tensors_held_by(*holders, depth: int = 3) -> list:
+    """Every tensor that ``holders`` - tensors, lists, tuples, dicts, objects with attributes - hold, ``depth`` levels down: what
+    a reconstructor keeps for as long as a captured step reads it (``torch.cuda.graph`` does not keep a capture's inputs)."""
+    found = []
+    for holder in holders:
+        if isinstance(holder, torch.Tensor):
+            found.append(holder)
+        elif depth > 0 and holder is not None:
+            inner = holder.values() if isinstance(holder, dict) else holder if isinstance(holder, (list, tuple)) else \
+                vars(holder).values() if hasattr(holder, "__dict__") else ()
+            found += tensors_held_by(*inner, depth=depth - 1)
+    return found
 
 
 def _gpu_device(device) -> torch.device:
@@ -147,12 +173,19 @@ class SurfaceReconstructor:
     """``artist.optim.SurfaceReconstructor``: see the module docstring; attributes as in the reference (:58-84).
 
     ``prepare`` / ``predict_flux`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_surfaces`` runs per group, for
-    callers that step themselves."""
+    callers that step themselves.
+
+    ``epoch_graph`` (a public attribute, read when a group's loop starts): replay each group's training step from an
+    ``artist_amd.EpochGraph`` (:meth:`build_epoch_graph`) instead of running it eagerly; the same bits, less host time per
+    epoch.  ``loss_definition`` must then not read the device (``.item()``, ``nonzero``, a host comparison): torch's capture
+    error propagates as it is, and there is no fall-back to the eager loop.  After a replay ``heliostat_group.active_surface_points``
+    / ``active_surface_normals`` are whatever the last eager call - the capture or a validation - left: a replay does not
+    look at the group's ``active_*`` attributes."""
 
     def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
                  dni: float | None = None, number_of_surface_points: torch.Tensor = torch.tensor([50, 50]),
                  bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), epsilon: float | None = 1e-12,
-                 plot_results: bool = False, device: torch.device | None = None) -> None:
+                 plot_results: bool = False, device: torch.device | None = None, epoch_graph: bool = False) -> None:
         if plot_results:
             raise NotImplementedError("plot_results=True: plotting stays ARTIST's (artist/optim/surface_reconstructor.py)")
         _gpu_device(device)
@@ -170,6 +203,7 @@ class SurfaceReconstructor:
         self.bitmap_resolution = torch.tensor([int(bitmap_resolution[0]), int(bitmap_resolution[1])])
         self.epsilon = epsilon
         self.plot_results = False
+        self.epoch_graph = bool(epoch_graph)
         self.validation_loss_pixel = PixelLoss()
         self.validation_loss_kl_div = KLDivergenceLoss()
 
@@ -256,9 +290,13 @@ class SurfaceReconstructor:
             if getattr(group, "kinematics", None) is not None:
                 orientations = group.kinematics.incident_ray_directions_to_orientations(
                     incident_ray_directions=incident, aim_points=aim_points, device=device)
+            elif state.static and kind in state.orientations:
+                orientations = state.orientations[kind]
             else:
                 from .scene import ideal_orientations
                 orientations = ideal_orientations(group.active_positions, aim_points, incident)
+                if state.static:            # (one of its constants comes from a host list: a copy that cannot be captured)
+                    state.orientations[kind] = orientations
         group._align(orientations)
 
         tracer = state.tracers.get(kind)
@@ -318,9 +356,14 @@ class SurfaceReconstructor:
                          violation=violation, alpha=alpha, smoothness=smoothness, beta=beta, ideal=ideal)
 
     def update_multiplier(self, state: GroupState, violation: torch.Tensor) -> None:
-        """``lambda <- clamp(lambda + rho * violation, min=0)`` per heliostat, after the backward pass (:1056-1062)."""
+        """``lambda <- clamp(lambda + rho * violation, min=0)`` per heliostat, after the backward pass (:1056-1062).  While a
+        captured step reads the multiplier (``state.static``) the same values are written into the same tensor."""
         with torch.no_grad():
-            state.multiplier = torch.clamp(state.multiplier + self.constraint_dict["rho_flux_integral"] * violation.detach(), min=0.0)
+            multiplier = torch.clamp(state.multiplier + self.constraint_dict["rho_flux_integral"] * violation.detach(), min=0.0)
+            if state.static:
+                state.multiplier.copy_(multiplier)
+            else:
+                state.multiplier = multiplier
 
     def validate(self, state: GroupState, device: torch.device | None = None) -> dict[str, torch.Tensor]:
         """The group's test samples under the current control points (:157-303), without gradient: ``{"pixel_loss", "kl_div"}``,
@@ -340,6 +383,47 @@ class SurfaceReconstructor:
         return losses
 
     # ------------------------------------------------------------------------------------------
+    def build_epoch_graph(self, state: GroupState, loss_definition, device: torch.device | None = None):
+        """The group's training step - :meth:`predict_flux`, :meth:`epoch_loss`, ``backward()`` - as an
+        ``artist_amd.EpochGraph`` (``state.graph``), built after :meth:`prepare` and before the control points' first use.
+        ``replay()`` leaves the gradient on ``nurbs_control_points`` and returns ``(the six history scalars [6], total loss per
+        heliostat, flux loss per sample, violation)``, detached, the bits of the eager step.
+
+        The warm-up runs make what an eager first epoch makes - the activation for the training samples, the training
+        tracer, ``state.reference_integrals`` - and nothing else: no step of the optimiser, the multiplier, the scheduler or
+        the early stopper.  From here on (``state.static``) :meth:`update_multiplier` writes in place, and the state keeps
+        every tensor that the captured step reads and that was made outside the capture (``state.kept``: the activation's
+        tables, which ``activate_heliostats`` rebinds and never writes, the reference integrals, the aim points, the rank's
+        rows), so that a validation is not handed their memory.  The step is not activated for training again after a
+        validation.  :meth:`close_epoch_graph` ends it."""
+        from . import graphs
+        device = _gpu_device(device)
+        parameter = state.group.nurbs_control_points
+        state.static = True
+
+        def step():
+            loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
+            loss.total.backward()
+            return loss.scalars(), loss.total_per_heliostat.detach(), loss.flux_loss_per_sample.detach(), loss.violation.detach()
+
+        try:
+            state.graph = graphs.EpochGraph(step, warmup=2, parameters=[parameter], device=device)
+        except BaseException:
+            self.close_epoch_graph(state)
+            raise
+        kinematics = getattr(state.group, "kinematics", None)
+        state.kept = tensors_held_by(state, state.group, kinematics, getattr(kinematics, "actuators", None))
+        return state.graph
+
+    def close_epoch_graph(self, state: GroupState) -> None:
+        """Close ``state.graph`` and let go of what was kept for it.  No autograd graph that was built on the graph's stream
+        outlives it: the surfaces the capture left on the group are detached."""
+        if state.graph is not None:
+            state.graph.close()
+        state.graph, state.static, state.kept = None, False, []
+        group = state.group
+        group.active_surface_points, group.active_surface_normals = group.active_surface_points.detach(), group.active_surface_normals.detach()
+
     def _synchronize_and_lock_gradients(self, parameter: torch.Tensor, device: torch.device | None = None) -> None:
         """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
         sub-world size.  Then the outer edges are locked (:749-788)."""
@@ -396,36 +480,45 @@ class SurfaceReconstructor:
             test_loss = None
             loss_host = float("inf")
             epoch = 0
-            while loss_host > tolerance and epoch <= max_epoch:
-                optimizer.zero_grad()
-                loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
-                loss.total.backward()
-                self.update_multiplier(state, loss.violation)
-                self._synchronize_and_lock_gradients(parameter, device)
-                optimizer.step()
-                # the epoch's scalars in ONE transfer, after the step has been queued
-                scalars = loss.scalars().tolist()
-                loss_host = scalars[0]
-                if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
-                    scheduler.step(loss_host)
-                else:
-                    scheduler.step()
-                stop = state.early_stopper.step(loss_host)
-                if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
-                    log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
-                    test_loss = self.validate(state, device)
-                if stop:
-                    log.info(f"Early stopping at epoch {epoch}.")
-                    break
-                for key, value in zip(HISTORY_KEYS, scalars):
-                    history[key].append(value)
-                epoch += 1
-            history["test_loss"] = test_loss
-            loss_history.append(history)
+            graph = self.build_epoch_graph(state, loss_definition, device) if self.epoch_graph else None
+            try:
+                while loss_host > tolerance and epoch <= max_epoch:
+                    optimizer.zero_grad()
+                    if graph is None:
+                        loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
+                        loss.total.backward()
+                        violation, total_per_heliostat = loss.violation, loss.total_per_heliostat
+                    else:
+                        scalars_on_device, total_per_heliostat, _, violation = graph.replay()
+                    self.update_multiplier(state, violation)
+                    self._synchronize_and_lock_gradients(parameter, device)
+                    optimizer.step()
+                    # the epoch's scalars in ONE transfer, after the step has been queued
+                    scalars = (loss.scalars() if graph is None else scalars_on_device).tolist()
+                    loss_host = scalars[0]
+                    if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+                        scheduler.step(loss_host)
+                    else:
+                        scheduler.step()
+                    stop = state.early_stopper.step(loss_host)
+                    if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
+                        log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
+                        test_loss = self.validate(state, device)
+                    if stop:
+                        log.info(f"Early stopping at epoch {epoch}.")
+                        break
+                    for key, value in zip(HISTORY_KEYS, scalars):
+                        history[key].append(value)
+                    epoch += 1
+                history["test_loss"] = test_loss
+                loss_history.append(history)
 
-            _, heliostat_rows = self._rank_rows(state, "train", device)
-            rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
-            final_loss_per_heliostat[rows + sum(sizes[:group_index])] = loss.total_per_heliostat.detach()
+                _, heliostat_rows = self._rank_rows(state, "train", device)
+                rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
+                final_loss_per_heliostat[rows + sum(sizes[:group_index])] = total_per_heliostat.detach()    # (the last replay's)
+            finally:
+                if graph is not None:
+                    self.close_epoch_graph(state)
             log.info(f"Rank: {rank}, Surfaces reconstructed.")
 
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history)

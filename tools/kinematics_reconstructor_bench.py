@@ -9,7 +9,10 @@ Both modes - flux-driven with ``FocalSpotLoss``, alignment-driven with ``AngleLo
   surface points, 10 rays, 256 x 256 bitmaps; measured from the true (zero) deviations, started 3e-3 rad away.
 
 An epoch is what the loop of ``reconstruct_kinematics`` does: ``zero_grad``, ``epoch_loss``, ``backward``, (``nan_to_num_``),
-``step``, ``loss.item()``, the scheduler.  A measurement is the host clock around ONE epoch, which ends in the loop's read of the
+``step``, ``loss.item()``, the scheduler - and, as ``<method>, epoch_graph``, the same with ``epoch_loss`` + ``backward`` replayed from
+the ``EpochGraph`` that ``epoch_graph=True`` builds (``build_epoch_graph``), eager and replayed alternating in one process; the
+build (warm-up + capture) is recorded in ms and in eager epochs, and ``replay_within_eager_spread`` says whether the replayed
+median stays within the eager median plus the eager p90 - p10 of the same call.  A measurement is the host clock around ONE epoch, which ends in the loop's read of the
 loss; warm-up epochs come first and are not counted; every epoch's time is kept, median and spread are reported.  Also recorded:
 the calls into the library per epoch by entry point (each is one kernel launch or a few), and the synchronising calls of one
 epoch, of an epoch with its validation and of the epoch after a validation, counted with ``torch.cuda.set_sync_debug_mode("warn")``.
@@ -87,7 +90,7 @@ def synthetic_case(method, heliostats=100, samples=4, rays=10, n_eval=50, resolu
 
 
 class Epoch:
-    def __init__(self, method, case):
+    def __init__(self, method, case, epoch_graph=False):
         from artist_amd import CalibrationSamples, FocalSpotLoss
         from artist_amd.optim import AngleLoss, KinematicsReconstructor
         scenario, six, resolution = case
@@ -97,16 +100,27 @@ class Epoch:
             optimization_configuration=CONFIGURATION, reconstruction_method=method, bitmap_resolution=resolution, device=DEV)
         self.loss_definition = FocalSpotLoss(scenario=scenario) if method == "raytracing" else AngleLoss()
         self.state = self.reconstructor.prepare(0, DEV)
+        self.graph = None
+        if epoch_graph:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            self.graph = self.reconstructor.build_epoch_graph(self.state, self.loss_definition, DEV)
+            torch.cuda.synchronize()
+            self.build_ms = 1e3 * (time.perf_counter() - t0)
 
     def step(self, validate=False):
         r, state = self.reconstructor, self.state
         state.optimizer.zero_grad()
-        loss = r.epoch_loss(state, self.loss_definition, DEV)
-        loss.total.backward()
+        if self.graph is None:
+            loss = r.epoch_loss(state, self.loss_definition, DEV)
+            loss.total.backward()
+            total = loss.total
+        else:
+            total, _, _ = self.graph.replay()
         if self.method == "alignment":
             state.optimizer.param_groups[0]["params"][0].grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
         state.optimizer.step()
-        host = loss.total.item()
+        host = total.item()
         state.scheduler.step()
         if validate:
             r.validate(state, DEV)
@@ -157,8 +171,11 @@ def count_calls(fn):
 
 
 def measure(name, make_case, epochs, blocks, warmup):
-    variants = {method: Epoch(method, make_case(method)) for method in METHODS}
-    times = {method: [] for method in METHODS}
+    variants = {}
+    for method in METHODS:                               # (each variant on a scenario of its own)
+        variants[method] = Epoch(method, make_case(method))
+        variants[f"{method}, epoch_graph"] = Epoch(method, make_case(method), epoch_graph=True)
+    times = {key: [] for key in variants}
     for epoch in variants.values():
         for _ in range(warmup):
             epoch.step()
@@ -182,6 +199,15 @@ def measure(name, make_case, epochs, blocks, warmup):
         print(f"[{name}] {method}: median {v['median_ms']:.3f} ms (min {v['min_ms']:.3f}, p10 {v['p10_ms']:.3f}, p90 {v['p90_ms']:.3f}, "
               f"max {v['max_ms']:.3f}); library calls {v['library_calls_total']}: {calls}; synchronising calls {v['synchronising_calls']}",
               flush=True)
+    for method in METHODS:
+        e, g = result[method], result[f"{method}, epoch_graph"]
+        g["eager_median_ms"], g["eager_over_replayed"] = e["median_ms"], e["median_ms"] / g["median_ms"]
+        g["eager_p90_minus_p10_ms"] = e["p90_ms"] - e["p10_ms"]
+        g["replay_within_eager_spread"] = g["median_ms"] <= e["median_ms"] + g["eager_p90_minus_p10_ms"]
+        g["build_ms"] = variants[f"{method}, epoch_graph"].build_ms
+        g["build_in_eager_epochs"] = g["build_ms"] / e["median_ms"]
+        print(f"[{name}] {method}, epoch_graph: eager / replayed {g['eager_over_replayed']:.2f}, build {g['build_ms']:.1f} ms = "
+              f"{g['build_in_eager_epochs']:.1f} eager epochs, within the eager spread: {g['replay_within_eager_spread']}", flush=True)
     return result
 
 

@@ -9,6 +9,9 @@ training samples each, 10 x 10 points per facet, 3 rays, 64 x 64 bitmaps) and 40
   (PixelLoss, constraint, both regularisers), backward, multiplier, edge lock, ``Adam.step()``, the epoch's six scalars in one
   ``tolist()`` (the synchronisation that ends the epoch), scheduler.
 * ``class+validation``: the same epoch followed by ``validate`` (and so by a re-activation in the next epoch).
+* ``class, epoch_graph`` / ``class+validation, epoch_graph``: the same two with the training step replayed from the
+  ``EpochGraph`` that ``epoch_graph=True`` builds (``build_epoch_graph``): zero_grad, ``replay()``, multiplier (in place), edge
+  lock, ``Adam.step()``, the six scalars, scheduler.  Also recorded: the build (warm-up + capture) in ms and in eager epochs.
 * ``assembled``: the epoch of ``bench.py``'s kind with one control net PER SAMPLE: fused NURBS + alignment, trace, fused
   crop + pixel loss, sum, backward, ``Adam.step()`` with the edge lock in the kernel, ``loss.item()``.  No constraint, no
   regularisers, no scheduler: the floor of what the kernels cost at this size.
@@ -16,7 +19,9 @@ training samples each, 10 x 10 points per facet, 3 rays, 64 x 64 bitmaps) and 40
 A measurement is the host clock around ONE epoch, which ends in a device synchronisation; warm-up epochs come first and are not
 counted; the variants alternate in blocks inside one process; every epoch's time is kept, median and spread are reported.  Also
 recorded: the synchronising calls of one epoch, counted with ``torch.cuda.set_sync_debug_mode("warn")``, and
-``reconstruct_surfaces`` as a whole (prepare, epochs, two validations, ``update_surfaces``) per epoch.
+``reconstruct_surfaces`` as a whole (prepare, epochs, two validations, ``update_surfaces``) per epoch, eagerly and with
+``epoch_graph=True``.  ``replay_within_eager_spread``: the replayed epoch's median does not exceed the eager median of the same
+call by more than that call's eager p90 - p10.
 
 usage: python tools/surface_reconstructor_bench.py [--out profiles/surface_reconstructor_bench.json] [--epochs 30] [--blocks 3]
 """
@@ -109,6 +114,31 @@ class ClassEpoch:
         return scalars[0]
 
 
+class GraphEpoch(ClassEpoch):
+    """The class epoch as ``reconstruct_surfaces`` runs it with ``epoch_graph=True``: the training step is a replay."""
+
+    def prepare(self):
+        super().prepare()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        self.graph = self.reconstructor.build_epoch_graph(self.state, self.loss_definition, DEV)
+        torch.cuda.synchronize()
+        self.build_ms = 1e3 * (time.perf_counter() - t0)
+
+    def step(self, validate=False):
+        r, state = self.reconstructor, self.state
+        state.optimizer.zero_grad()
+        scalars, _, _, violation = self.graph.replay()
+        r.update_multiplier(state, violation)
+        r._synchronize_and_lock_gradients(state.group.nurbs_control_points, DEV)
+        state.optimizer.step()
+        scalars = scalars.tolist()
+        state.scheduler.step()
+        if validate:
+            r.validate(state, DEV)
+        return scalars[0]
+
+
 class AssembledEpoch:
     """bench.py's epoch at the same number of traced samples: one control net per sample."""
 
@@ -178,7 +208,9 @@ def count_syncs(fn):
 
 
 def measure(name, case, epochs, blocks, warmup):
-    variants = {"class": (ClassEpoch(case), False), "class+validation": (ClassEpoch(case), True), "assembled": (AssembledEpoch(case), False)}
+    variants = {"class": (ClassEpoch(case), False), "class, epoch_graph": (GraphEpoch(case), False),
+                "class+validation": (ClassEpoch(case), True), "class+validation, epoch_graph": (GraphEpoch(case), True),
+                "assembled": (AssembledEpoch(case), False)}
     times = {key: [] for key in variants}
     for key, (epoch, validate) in variants.items():
         epoch.prepare()
@@ -197,7 +229,17 @@ def measure(name, case, epochs, blocks, warmup):
         "epoch (the loop's tolist)": count_syncs(lambda: variants["class"][0].step(False)),
         "epoch + validation": count_syncs(lambda: variants["class+validation"][0].step(True)),
         "epoch after a validation (re-activation)": count_syncs(lambda: variants["class+validation"][0].step(False)),
-        "assembled": count_syncs(lambda: variants["assembled"][0].step(False))}
+        "assembled": count_syncs(lambda: variants["assembled"][0].step(False)),
+        "epoch_graph: epoch (the loop's tolist)": count_syncs(lambda: variants["class, epoch_graph"][0].step(False)),
+        "epoch_graph: epoch + validation": count_syncs(lambda: variants["class+validation, epoch_graph"][0].step(True)),
+        "epoch_graph: epoch after a validation (no re-activation)": count_syncs(lambda: variants["class+validation, epoch_graph"][0].step(False))}
+    for eager, replayed in (("class", "class, epoch_graph"), ("class+validation", "class+validation, epoch_graph")):
+        e, g = result[eager], result[replayed]
+        g["eager_median_ms"], g["eager_over_replayed"] = e["median_ms"], e["median_ms"] / g["median_ms"]
+        g["eager_p90_minus_p10_ms"] = e["p90_ms"] - e["p10_ms"]
+        g["replay_within_eager_spread"] = g["median_ms"] <= e["median_ms"] + g["eager_p90_minus_p10_ms"]
+        g["build_ms"] = variants[replayed][0].build_ms
+        g["build_in_eager_epochs"] = g["build_ms"] / e["median_ms"]
     # the whole call: prepare, max_epoch + 1 epochs, validations after the first and the last but one, update_surfaces
     run_epochs = max(epochs, 4)
     whole = ClassEpoch(case, max_epoch=run_epochs - 1)
@@ -207,9 +249,22 @@ def measure(name, case, epochs, blocks, warmup):
     torch.cuda.synchronize()
     result["reconstruct_surfaces"] = dict(total_ms=1e3 * (time.perf_counter() - t0), epochs=len(histories[0][0]["total_loss"]))
     result["reconstruct_surfaces"]["ms_per_epoch"] = result["reconstruct_surfaces"]["total_ms"] / result["reconstruct_surfaces"]["epochs"]
+    whole = ClassEpoch(case, max_epoch=run_epochs - 1)
+    whole.reconstructor.epoch_graph = True
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _, histories = whole.reconstructor.reconstruct_surfaces(whole.loss_definition, DEV)
+    torch.cuda.synchronize()
+    result["reconstruct_surfaces, epoch_graph"] = dict(total_ms=1e3 * (time.perf_counter() - t0), epochs=len(histories[0][0]["total_loss"]))
+    result["reconstruct_surfaces, epoch_graph"]["ms_per_epoch"] = \
+        result["reconstruct_surfaces, epoch_graph"]["total_ms"] / result["reconstruct_surfaces, epoch_graph"]["epochs"]
     print(f"[{name}] " + ", ".join(f"{key}: median {v['median_ms']:.3f} ms (min {v['min_ms']:.3f}, p10 {v['p10_ms']:.3f}, p90 {v['p90_ms']:.3f}, "
                                    f"max {v['max_ms']:.3f})" for key, v in result.items() if "median_ms" in v), flush=True)
-    print(f"[{name}] synchronising calls: {result['synchronising_calls']}; reconstruct_surfaces: {result['reconstruct_surfaces']}", flush=True)
+    print(f"[{name}] synchronising calls: {result['synchronising_calls']}; reconstruct_surfaces: {result['reconstruct_surfaces']}; "
+          f"with epoch_graph: {result['reconstruct_surfaces, epoch_graph']}", flush=True)
+    for key in ("class, epoch_graph", "class+validation, epoch_graph"):
+        print(f"[{name}] {key}: " + ", ".join(f"{k} {v:.3f}" if isinstance(v, float) else f"{k} {v}" for k, v in result[key].items()
+                                                if k not in ("all_ms",)), flush=True)
     return result
 
 
