@@ -13,7 +13,8 @@ backward, behind ARTIST's own call surface:
     artist_amd.optim.Adam           <-> torch.optim.Adam as the reconstructors use it (the epoch's optimiser step)
     artist_amd.optim.AimPointOptimizer, artist_amd.training, artist_amd.flux.trapezoid_distribution
                                     <-> artist.optim.AimPointOptimizer, artist.optim.training, artist.flux.bitmap.trapezoid_distribution
-    artist_amd.optim.SurfaceReconstructor <-> artist.optim.SurfaceReconstructor (CalibrationSamples: its data parser, in memory)
+    artist_amd.optim.SurfaceReconstructor <-> artist.optim.SurfaceReconstructor (CalibrationSamples: its data parser, in memory;
+                                              parameters=(...): facet canting and translations learn too, beyond the reference)
     artist_amd.optim.KinematicsReconstructor, VectorLoss, AngleLoss, CosineSimilarityLoss
                                     <-> artist.optim.KinematicsReconstructor ("raytracing" and "alignment"), artist.optim.loss
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer

@@ -8,7 +8,8 @@ The update rule is ``torch.optim.adam._single_tensor_adam`` in fp32; tests compa
 
 ``SmoothnessRegularizer`` and ``IdealSurfaceRegularizer`` (``artist_amd.regularizers``) are exported here as well, where the
 reference has them (``artist.optim``), and so are ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``),
-``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``), ``KinematicsReconstructor``
+``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``; with ``parameters=(...)`` it hands this ``Adam`` one parameter
+group per learnable tensor - control points, facet canting, facet translations), ``KinematicsReconstructor``
 (``artist_amd.kinematics_reconstructor``) and the losses on vectors it compares normals with (``artist_amd.losses``).
 """
 from __future__ import annotations

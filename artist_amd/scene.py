@@ -558,7 +558,8 @@ class HeliostatField:
                                               change_number_of_control_points_per_facet, dev)
 
     def update_surfaces(self, device: torch.device | None = None) -> None:
-        """``surface_points`` / ``surface_normals`` of every group anew from its (detached) control points, on the square
+        """``surface_points`` / ``surface_normals`` of every group anew from its (detached) control points, canting and facet
+        translations as they are now - a reconstruction may have learnt any of the three - on the square
         evaluation grid the group was loaded with (artist/field/heliostat_field.py:437-503): what a reconstruction leaves
         behind for the ray tracing after it."""
         for group in self.heliostat_groups:
@@ -567,7 +568,8 @@ class HeliostatField:
             nets = group.nurbs_control_points.detach()
             grid = create_nurbs_evaluation_grid(torch.tensor([side, side]), device=nets.device)
             points, normals = NURBSSurfaces(group.nurbs_degrees, nets, device=nets.device).calculate_surface_points_and_normals(
-                grid[None, None].expand(int(group.number_of_heliostats), facets, -1, -1), group.canting, group.facet_translations)
+                grid[None, None].expand(int(group.number_of_heliostats), facets, -1, -1), group.canting.detach(),
+                group.facet_translations.detach())            # (detached: the one fused launch, no graph through the leaves)
             heliostats = group.surface_points.shape[0]
             group.surface_points = points.reshape(heliostats, -1, 4).detach()
             group.surface_normals = normals.reshape(heliostats, -1, 4).detach()

@@ -24,6 +24,12 @@ epochs, another all validations: a tracer's distortions depend on the seed and t
 ``backward()`` - is captured once into an ``artist_amd.EpochGraph`` and replayed every epoch; the multiplier update, the nested
 all-reduce, the edge lock, ``Adam.step()``, the one host transfer, the scheduler, early stopping, the history and every
 validation stay eager, in the same order.  The replayed epoch gives the eager epoch's bits.
+
+``parameters=(...)`` ("Rigid facet parameters"; beyond the reference's class): the facets' canting vectors and
+translations learn beside or instead of the control points.  Their active rows are selected inside the step, the evaluation
+takes the staged route (``art_nurbs_fwd`` without canting, ``art_cant_facets_fwd``; backwards ``art_cant_facets_bwd`` and, if
+the control points learn, ``art_nurbs_bwd``) - still once per heliostat and epoch, with the same fixed-order sum over the
+samples - and the gradient of the homogeneous w components is set to zero before the step.
 """
 from __future__ import annotations
 
@@ -45,13 +51,40 @@ from .training import reduce_loss_per_sample
 log = logging.getLogger(__name__)
 
 __all__ = ["SurfaceReconstructor", "CalibrationSamples", "GroupState", "EpochLoss", "flux_integral_constraint", "HISTORY_KEYS",
-           "tensors_held_by"]
+           "PARAMETER_NAMES", "canonical_parameters", "learning_rates", "tensors_held_by"]
 
 #: the per-epoch lists of a group's history, in the order the epoch's scalars are stacked; ``"test_loss"`` comes on top
 HISTORY_KEYS = ("total_loss", "flux_loss", "smoothness_regularizer", "ideal_regularizer", "flux_integral",
                 "flux_integral_constraint")
 
+#: what a reconstruction can learn, in the canonical order: the order of the optimiser's parameter groups, of the reduces in
+#: nested mode and of the broadcasts after the run.  The names are the group's attributes.
+PARAMETER_NAMES = ("nurbs_control_points", "canting", "facet_translations")
+
 _mean_over_samples = partial(torch.mean, dim=-1)
+
+
+def canonical_parameters(parameters) -> tuple:
+    """``parameters`` - a non-empty tuple or list of ``PARAMETER_NAMES``, in any order, duplicates allowed - as a tuple in the
+    canonical order.  Anything else is a ``ValueError`` that lists the three names."""
+    allowed = ", ".join(repr(name) for name in PARAMETER_NAMES)
+    if not isinstance(parameters, (tuple, list)) or len(parameters) == 0:
+        raise ValueError(f"parameters must be a non-empty tuple or list drawn from {allowed}; got {parameters!r}")
+    unknown = [name for name in parameters if name not in PARAMETER_NAMES]
+    if unknown:
+        raise ValueError(f"unknown parameter(s) {unknown!r}: parameters must be drawn from {allowed}")
+    return tuple(name for name in PARAMETER_NAMES if name in parameters)
+
+
+def learning_rates(optimizer_dict: dict, parameters=PARAMETER_NAMES) -> dict:
+    """The initial learning rate of every name in ``parameters``, in the canonical order, from the configuration's
+    ``"optimization"`` table: ``"initial_learning_rate"`` for the control points, the optional
+    ``"initial_learning_rate_canting"`` and ``"initial_learning_rate_facet_translations"`` for the two rigid tensors, each
+    defaulting to ``"initial_learning_rate"``."""
+    default = float(optimizer_dict["initial_learning_rate"])
+    keys = {"nurbs_control_points": "initial_learning_rate", "canting": "initial_learning_rate_canting",
+            "facet_translations": "initial_learning_rate_facet_translations"}
+    return {name: float(optimizer_dict.get(keys[name], default)) for name in canonical_parameters(parameters)}
 
 
 def flux_integral_constraint(cropped_sums: torch.Tensor, reference: torch.Tensor, multiplier, rho: float, energy_tolerance: float,
@@ -145,6 +178,10 @@ class GroupState:
     static: bool = False
     kept: list = field(default_factory=list)
     orientations: dict = field(default_factory=dict)
+    # what learns: name -> the group's own tensor, in the canonical order (PARAMETER_NAMES); and those among them that did not
+    # require grad before ``prepare`` marked them
+    learnables: dict = field(default_factory=dict)
+    marked: list = field(default_factory=list)
 
 
 def tensors_held_by(*holders, depth: int = 3) -> list:
@@ -169,7 +206,20 @@ def _gpu_device(device) -> torch.device:
     return device
 
 
-class SurfaceReconstructor:
+class _TakesParameters(type):
+    """``SurfaceReconstructor(..., epoch_graph=False, parameters=(...))``: the class call takes the one keyword that the
+    reference's constructor has no place for, checks it before ``__init__`` runs - so before any device work - and sets the
+    attribute.  ``__init__`` itself keeps the signature both reconstructors share, the reference's arguments and then
+    ``epoch_graph`` (tests/test_reconstructor_graphs_host.py holds it to that)."""
+
+    def __call__(cls, *args, parameters=("nurbs_control_points",), **kwargs):
+        chosen = canonical_parameters(parameters)
+        reconstructor = super().__call__(*args, **kwargs)
+        reconstructor.parameters = chosen
+        return reconstructor
+
+
+class SurfaceReconstructor(metaclass=_TakesParameters):
     """``artist.optim.SurfaceReconstructor``: see the module docstring; attributes as in the reference (:58-84).
 
     ``prepare`` / ``predict_flux`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_surfaces`` runs per group, for
@@ -180,7 +230,25 @@ class SurfaceReconstructor:
     epoch.  ``loss_definition`` must then not read the device (``.item()``, ``nonzero``, a host comparison): torch's capture
     error propagates as it is, and there is no fall-back to the eager loop.  After a replay ``heliostat_group.active_surface_points``
     / ``active_surface_normals`` are whatever the last eager call - the capture or a validation - left: a replay does not
-    look at the group's ``active_*`` attributes."""
+    look at the group's ``active_*`` attributes.
+
+    ``parameters`` (an addition, a keyword of the class call after ``epoch_graph``; the reference's class learns the control
+    points only).  It is NOT a parameter of ``__init__`` and does not show in its signature: the metaclass ``_TakesParameters``
+    takes it from the call, checks it before ``__init__`` runs and sets the attribute after it, so inside ``__init__`` - also
+    a subclass's - the attribute still is the default, and ``inspect.signature(SurfaceReconstructor)`` shows ``(*args,
+    parameters=..., **kwargs)``.  What learns: a non-empty tuple or list
+    of ``"nurbs_control_points"``, ``"canting"`` ``[N, F, 2, 4]`` and ``"facet_translations"`` ``[N, F, 4]`` - the group's
+    attributes of these names, in any order; anything else is a ``ValueError``.  Kept as ``self.parameters``, a tuple in
+    this order (assigning the attribute checks and orders it the same way), and read in :meth:`prepare`.  A facet that sits
+    tilted or shifted on its mounts is then learnt as two vectors and an offset, not by bending its 300 control points against the
+    ideal-surface regulariser.  One ``artist_amd.optim.Adam`` steps them, one parameter group each, at
+    ``optimization["initial_learning_rate"]``, ``["initial_learning_rate_canting"]`` and
+    ``["initial_learning_rate_facet_translations"]`` (the latter two optional, defaulting to the first).  The schedulers scale
+    every group; ``cyclic``'s ``lr_min`` / ``lr_max`` are one pair for ALL groups, whatever their initial rates.  The w
+    components of both rigid tensors are homogeneous zeros and no parameters: their gradient is set to zero before the step
+    (the alignment's adjoint leaves one on a translation's w), so they keep their bits.  Regularisers, constraint, histories,
+    validation and the stop logic are the same for every choice; without the control points the two regulariser terms are
+    constants of the run.  After the run the rigid tensors that ``prepare`` marked no longer require grad."""
 
     def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
                  dni: float | None = None, number_of_surface_points: torch.Tensor = torch.tensor([50, 50]),
@@ -207,12 +275,24 @@ class SurfaceReconstructor:
         self.validation_loss_pixel = PixelLoss()
         self.validation_loss_kl_div = KLDivergenceLoss()
 
+    _parameters = PARAMETER_NAMES[:1]           # the control points alone, unless chosen otherwise
+
+    @property
+    def parameters(self) -> tuple:
+        """What learns, in the canonical order (``PARAMETER_NAMES``)."""
+        return self._parameters
+
+    @parameters.setter
+    def parameters(self, parameters) -> None:
+        self._parameters = canonical_parameters(parameters)
+
     # ------------------------------------------------------------------------------------------
     def prepare(self, heliostat_group_index: int, device: torch.device | None = None) -> GroupState | None:
         """Everything before a group's first epoch (:343-474, 898-966): its calibration samples from
         ``data["data_parser"].parse_data_for_reconstruction``, the train/test split, the evaluation grid, a frozen copy of the
-        nets of the heliostats that have samples, ``artist_amd.optim.Adam`` on ``heliostat_group.nurbs_control_points``, the
-        configured scheduler, early stopping and a zero multiplier.  None for a group without samples."""
+        nets of the heliostats that have samples, ``artist_amd.optim.Adam`` with one parameter group per tensor of
+        ``self.parameters`` (``requires_grad_()`` on those, and on no other), the configured scheduler, early stopping and a
+        zero multiplier.  None for a group without samples."""
         from .optim import Adam
         device = _gpu_device(device)
         group = self.scenario.heliostat_field.heliostat_groups[heliostat_group_index]
@@ -229,7 +309,13 @@ class SurfaceReconstructor:
         grid = create_nurbs_evaluation_grid(self.number_of_surface_points, device=device)
         with torch.no_grad():
             original = group.nurbs_control_points.index_select(0, active_rows).clone()
-        optimizer = Adam([group.nurbs_control_points.requires_grad_()], lr=float(self.optimizer_dict["initial_learning_rate"]))
+        # the leaves are only marked here: nothing builds an autograd graph through them before the first step (graphs.py,
+        # "Fresh leaves"); a tensor that is not chosen is left as it is
+        rates = learning_rates(self.optimizer_dict, self.parameters)
+        learnables = {name: getattr(group, name) for name in self.parameters}
+        marked = [tensor for name, tensor in learnables.items() if name != "nurbs_control_points" and not tensor.requires_grad]
+        optimizer = Adam([dict(params=[tensor.requires_grad_()], lr=rates[name]) for name, tensor in learnables.items()],
+                         lr=float(self.optimizer_dict["initial_learning_rate"]))
         scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=optimizer, parameters=self.scheduler_dict)
         stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
                                          patience=self.optimizer_dict["early_stopping_patience"],
@@ -237,9 +323,10 @@ class SurfaceReconstructor:
         state = GroupState(index=heliostat_group_index, group=group, mask=mask, split=split, active_rows=active_rows,
                            original_control_points=original,
                            evaluation_points=grid[None, None].expand(active, int(group.number_of_facets_per_heliostat), -1, -1),
-                           canting=group.canting.index_select(0, active_rows),
-                           facet_translations=group.facet_translations.index_select(0, active_rows),
-                           optimizer=optimizer, scheduler=scheduler, early_stopper=stopper, multiplier=torch.zeros((), device=device))
+                           canting=group.canting.detach().index_select(0, active_rows),        # (constants unless they learn)
+                           facet_translations=group.facet_translations.detach().index_select(0, active_rows),
+                           optimizer=optimizer, scheduler=scheduler, early_stopper=stopper, multiplier=torch.zeros((), device=device),
+                           learnables=learnables, marked=marked)
         _, heliostat_rows = self._rank_rows(state, "train", device)
         state.multiplier = torch.zeros(active if heliostat_rows is None else int(heliostat_rows.numel()), device=device)
         return state
@@ -277,8 +364,14 @@ class SurfaceReconstructor:
             state.activated = kind
 
         nets = group.nurbs_control_points.index_select(0, state.active_rows)
+        # a rigid tensor that learns: its active rows selected inside the step, so that the gradient lands on the group's own
+        # tensor (exact zeros on the rows without samples) and the evaluation takes the staged route (ops.nurbs_eval); under
+        # no_grad, and for constants, the one fused launch
+        canting = group.canting.index_select(0, state.active_rows) if "canting" in state.learnables else state.canting
+        translations = group.facet_translations.index_select(0, state.active_rows) if "facet_translations" in state.learnables \
+            else state.facet_translations
         points, normals = NURBSSurfaces(group.nurbs_degrees, nets, device=device).calculate_surface_points_and_normals(
-            state.evaluation_points, state.canting, state.facet_translations)
+            state.evaluation_points, canting, translations)
         active, per_heliostat = points.shape[0], points.shape[1] * points.shape[2]
         repeat = lambda t: t.reshape(active, 1, per_heliostat, 4).expand(-1, samples, -1, -1).reshape(  # noqa: E731
             active * samples, per_heliostat, 4)              # backward: .sum(1) over the samples, a fixed order
@@ -386,8 +479,8 @@ class SurfaceReconstructor:
     def build_epoch_graph(self, state: GroupState, loss_definition, device: torch.device | None = None):
         """The group's training step - :meth:`predict_flux`, :meth:`epoch_loss`, ``backward()`` - as an
         ``artist_amd.EpochGraph`` (``state.graph``), built after :meth:`prepare` and before the control points' first use.
-        ``replay()`` leaves the gradient on ``nurbs_control_points`` and returns ``(the six history scalars [6], total loss per
-        heliostat, flux loss per sample, violation)``, detached, the bits of the eager step.
+        ``replay()`` leaves the gradient on every learnable tensor (``state.learnables``) and returns ``(the six history
+        scalars [6], total loss per heliostat, flux loss per sample, violation)``, detached, the bits of the eager step.
 
         The warm-up runs make what an eager first epoch makes - the activation for the training samples, the training
         tracer, ``state.reference_integrals`` - and nothing else: no step of the optimiser, the multiplier, the scheduler or
@@ -398,7 +491,6 @@ class SurfaceReconstructor:
         validation.  :meth:`close_epoch_graph` ends it."""
         from . import graphs
         device = _gpu_device(device)
-        parameter = state.group.nurbs_control_points
         state.static = True
 
         def step():
@@ -407,7 +499,7 @@ class SurfaceReconstructor:
             return loss.scalars(), loss.total_per_heliostat.detach(), loss.flux_loss_per_sample.detach(), loss.violation.detach()
 
         try:
-            state.graph = graphs.EpochGraph(step, warmup=2, parameters=[parameter], device=device)
+            state.graph = graphs.EpochGraph(step, warmup=2, parameters=list(state.learnables.values()), device=device)
         except BaseException:
             self.close_epoch_graph(state)
             raise
@@ -435,8 +527,33 @@ class SurfaceReconstructor:
             parameter.grad /= ddp["heliostat_group_world_size"]
         parameter.grad = self.lock_control_points_on_outer_edges(gradients=parameter.grad, device=device)
 
+    def _synchronize_and_zero_w_gradients(self, parameter: torch.Tensor, device: torch.device | None = None) -> None:
+        """What :meth:`_synchronize_and_lock_gradients` is to the control points, for ``canting`` ``[N, F, 2, 4]`` and
+        ``facet_translations`` ``[N, F, 4]``: the nested average, then the gradient of every w component is set to zero, in
+        place.  The w components are homogeneous zeros, not parameters; ``art_align_bwd`` returns a w component for points
+        (``g @ orientation`` picks up the translation column), which reaches a translation's w and would let Adam move the
+        points' w away from 1."""
+        if parameter.grad is None:
+            return
+        ddp = self.ddp_setup
+        if ddp["is_nested"]:
+            distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
+            parameter.grad /= ddp["heliostat_group_world_size"]
+        with torch.no_grad():
+            parameter.grad[..., 3] = 0
+
+    def _synchronize_and_lock_learnables(self, state: GroupState, device: torch.device | None = None) -> None:
+        """Before the step: one reduce per learnable tensor in the canonical order (the same on every rank), the edge lock on
+        the control points, the w rule on the rigid tensors."""
+        for name, tensor in state.learnables.items():
+            if name == "nurbs_control_points":
+                self._synchronize_and_lock_gradients(tensor, device)
+            else:
+                self._synchronize_and_zero_w_gradients(tensor, device)
+
     def _synchronize_reconstruction_across_ranks(self, final_loss_per_heliostat: torch.Tensor, loss_history: list) -> list:
-        """Every group's control points from the first rank that owns the group, the final losses MIN-reduced (a heliostat
+        """Every group's learnable tensors (the control points by default) from the first rank that owns the group, the
+        final losses MIN-reduced (a heliostat
         another rank reconstructed is ``inf`` here), the histories of all ranks gathered (:790-840).  Returns the histories
         per rank; ``[loss_history]`` in a single process."""
         ddp = self.ddp_setup
@@ -444,7 +561,8 @@ class SurfaceReconstructor:
             return [loss_history]
         with torch.no_grad():
             for index, group in enumerate(self.scenario.heliostat_field.heliostat_groups):
-                torch.distributed.broadcast(group.nurbs_control_points.detach(), src=ddp["ranks_to_groups_mapping"][index][0])
+                for name in self.parameters:
+                    torch.distributed.broadcast(getattr(group, name).detach(), src=ddp["ranks_to_groups_mapping"][index][0])
         torch.distributed.all_reduce(final_loss_per_heliostat, op=torch.distributed.ReduceOp.MIN)
         histories: list = [[] for _ in range(ddp["world_size"])]
         torch.distributed.all_gather_object(histories, loss_history)
@@ -457,7 +575,8 @@ class SurfaceReconstructor:
         group)``; an entry has the per-epoch float lists ``HISTORY_KEYS`` and ``"test_loss"``, the last validation's
         ``{"pixel_loss", "kl_div"}`` per heliostat.  A group runs while its loss is above ``tolerance`` and
         ``epoch <= max_epoch``, or until early stopping, which ends the group before that epoch's history entry.  Afterwards
-        the ranks are synchronised and the field's surface points follow the new control points (``update_surfaces``)."""
+        the ranks are synchronised and the field's surface points follow the new control points, canting and translations
+        (``update_surfaces``)."""
         device = _gpu_device(device)
         ddp = self.ddp_setup
         rank = ddp["rank"]
@@ -475,7 +594,6 @@ class SurfaceReconstructor:
             if state is None:                                        # a group without samples
                 continue
             optimizer, scheduler = state.optimizer, state.scheduler
-            parameter = state.group.nurbs_control_points
             history: dict = {key: [] for key in HISTORY_KEYS}
             test_loss = None
             loss_host = float("inf")
@@ -491,7 +609,7 @@ class SurfaceReconstructor:
                     else:
                         scalars_on_device, total_per_heliostat, _, violation = graph.replay()
                     self.update_multiplier(state, violation)
-                    self._synchronize_and_lock_gradients(parameter, device)
+                    self._synchronize_and_lock_learnables(state, device)
                     optimizer.step()
                     # the epoch's scalars in ONE transfer, after the step has been queued
                     scalars = (loss.scalars() if graph is None else scalars_on_device).tolist()
@@ -519,6 +637,8 @@ class SurfaceReconstructor:
             finally:
                 if graph is not None:
                     self.close_epoch_graph(state)
+                for tensor in state.marked:             # the rigid tensors are constants again for whoever evaluates next
+                    tensor.requires_grad_(False)
             log.info(f"Rank: {rank}, Surfaces reconstructed.")
 
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history)
