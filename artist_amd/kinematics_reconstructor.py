@@ -26,6 +26,13 @@ is captured once into an ``artist_amd.EpochGraph`` and replayed every epoch, in 
 nested all-reduce, ``Adam.step()``, the one host read, the scheduler, early stopping, the history and every validation stay eager,
 in the same order.  The replayed epoch gives the eager epoch's bits.
 
+``parameters=(...)`` ("More kinematic parameters"; beyond the reference's class): the translation deviations
+``[H, 9]`` and the optimisable actuator parameters ``[H, 2, 2]`` learn beside or instead of the rotation deviations.
+``art_rigid_body_bwd`` writes all three gradients in its one launch anyway; a tensor that learns is bound to the kinematics'
+per-sample table the way the rotation deviations are - unique rows, expanded with a view, the same fixed-order sum backwards -
+and one ``artist_amd.optim.Adam`` steps one parameter group per tensor.  An epoch calls the library as before, but for one
+``art_adam_step`` per further tensor.
+
 More than one rank has not run on a GPU: the collectives (``_synchronize_gradients_nested_ddp``,
 ``_synchronize_reconstruction_across_ranks``) are tested with two gloo processes on CPU tensors.
 """
@@ -42,17 +49,27 @@ from . import _lib, distributed, training
 from ._memo import Memo
 from .flux import FocalSpotLoss, KLDivergenceLoss, PixelLoss
 from .raytracing import HeliostatRayTracer
-from .surface_reconstructor import tensors_held_by
+from .surface_reconstructor import LearnsParameters, learning_rates, tensors_held_by
 from .training import reduce_loss_per_sample
 
 log = logging.getLogger(__name__)
 
 __all__ = ["KinematicsReconstructor", "KinematicsGroupState", "KinematicsEpochLoss", "KINEMATICS_RECONSTRUCTION_RAYTRACING",
-           "KINEMATICS_RECONSTRUCTION_ALIGNMENT"]
+           "KINEMATICS_RECONSTRUCTION_ALIGNMENT", "KINEMATICS_PARAMETER_NAMES", "KINEMATICS_LEARNING_RATE_KEYS"]
 
 #: the two reconstruction methods (artist/util/constants.py)
 KINEMATICS_RECONSTRUCTION_RAYTRACING = "raytracing"
 KINEMATICS_RECONSTRUCTION_ALIGNMENT = "alignment"
+
+#: what a reconstruction can learn, in the canonical order: the order of the optimiser's parameter groups and of the reduces
+#: in nested mode.  ``kinematics.rotation_deviation_parameters`` ``[H, 4]``, ``kinematics.translation_deviation_parameters``
+#: ``[H, 9]`` and ``kinematics.actuators.optimizable_parameters`` ``[H, 2, 2]``.
+KINEMATICS_PARAMETER_NAMES = ("rotation_deviations", "translation_deviations", "actuator_parameters")
+
+#: the configuration key of every name's initial learning rate; the first is required and the default of the others
+KINEMATICS_LEARNING_RATE_KEYS = {"rotation_deviations": "initial_learning_rate_rotation_deviation",
+                                 "translation_deviations": "initial_learning_rate_translation_deviation",
+                                 "actuator_parameters": "initial_learning_rate_actuator_parameters"}
 
 _mean_over_samples = partial(torch.mean, dim=-1)
 _median_over_samples = partial(torch.median, dim=1)
@@ -90,6 +107,16 @@ class KinematicsGroupState:
     # epoch_graph: the captured training step and what is kept alive for it
     graph: Any = None
     kept: list = field(default_factory=list)
+    # what learns: name -> the kinematics' own tensor, in the canonical order (KINEMATICS_PARAMETER_NAMES)
+    learnables: dict = field(default_factory=dict)
+
+
+def _slot(kinematics, name: str) -> tuple:
+    """Where the tensor ``name`` lives: ``(holder, its attribute, the attribute of its per-sample table)``."""
+    if name == "actuator_parameters":
+        return kinematics.actuators, "optimizable_parameters", "active_optimizable_parameters"
+    stem = {"rotation_deviations": "rotation_deviation_parameters", "translation_deviations": "translation_deviation_parameters"}[name]
+    return kinematics, stem, "active_" + stem
 
 
 def _gpu_device(device) -> torch.device:
@@ -100,7 +127,7 @@ def _gpu_device(device) -> torch.device:
     return device
 
 
-class KinematicsReconstructor:
+class KinematicsReconstructor(LearnsParameters):
     """``artist.optim.KinematicsReconstructor``: see the module docstring; attributes as in the reference (:38-60).
 
     ``prepare`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_kinematics`` runs per group, for callers that step
@@ -111,7 +138,21 @@ class KinematicsReconstructor:
     time per epoch.  ``loss_definition`` must then not read the device (``.item()``, ``nonzero``, a host comparison): torch's
     capture error propagates as it is, and there is no fall-back to the eager loop.  After a replay
     ``heliostat_group.active_surface_points`` / ``active_surface_normals`` and the kinematics' ``active_*`` tables are whatever
-    the last eager call - the capture or a validation - left: a replay does not look at them."""
+    the last eager call - the capture or a validation - left: a replay does not look at them.
+
+    ``parameters`` (an addition, a keyword of the class call after ``epoch_graph``, taken the way ``SurfaceReconstructor``
+    takes its own - ``__init__`` keeps the reference's signature; the reference's class learns the rotation deviations only).
+    What learns: a non-empty tuple or list of ``KINEMATICS_PARAMETER_NAMES`` - ``"rotation_deviations"``
+    (``kinematics.rotation_deviation_parameters``), ``"translation_deviations"`` (``kinematics.translation_deviation_parameters``)
+    and ``"actuator_parameters"`` (``kinematics.actuators.optimizable_parameters``: the linear actuators' initial angles and
+    stroke lengths) - in any order; anything else is a ``ValueError``.  Kept as ``self.parameters``, a tuple in this order, and
+    read in :meth:`prepare`, which refuses (``ValueError``) the translations in the alignment-driven mode - they do not enter
+    the predicted normal, their gradient is identically zero - and the actuator parameters of a group with ideal actuators.
+    One ``artist_amd.optim.Adam`` steps them, one parameter group each, at
+    ``optimization["initial_learning_rate_rotation_deviation"]``, ``["initial_learning_rate_translation_deviation"]`` and
+    ``["initial_learning_rate_actuator_parameters"]`` (the latter two optional, defaulting to the first); the schedulers
+    scale every group.  Loss, validation, histories and the stop logic are the same for every choice.  Every learned tensor
+    is detached at the end of :meth:`reconstruct_kinematics`; a tensor that is not chosen is never marked and never written."""
 
     def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
                  dni: float | None = None, reconstruction_method: str = KINEMATICS_RECONSTRUCTION_RAYTRACING,
@@ -136,6 +177,8 @@ class KinematicsReconstructor:
         self.reconstruction_method = reconstruction_method
         self.epoch_graph = bool(epoch_graph)
 
+    PARAMETER_NAMES = KINEMATICS_PARAMETER_NAMES        # (the rotation deviations alone, unless chosen otherwise)
+
     @property
     def _flux_driven(self) -> bool:
         return self.reconstruction_method == KINEMATICS_RECONSTRUCTION_RAYTRACING
@@ -144,11 +187,19 @@ class KinematicsReconstructor:
     def prepare(self, heliostat_group_index: int, device: torch.device | None = None) -> KinematicsGroupState | None:
         """Everything before a group's first epoch (:332-419, 758-794, 937-964): its calibration samples from
         ``data["data_parser"].parse_data_for_reconstruction``, the train/test split, in alignment mode the measured normals,
-        ``artist_amd.optim.Adam`` on ``kinematics.rotation_deviation_parameters``, the configured scheduler and early
-        stopping.  None for a group without samples."""
+        ``artist_amd.optim.Adam`` with one parameter group per tensor of ``self.parameters`` (``requires_grad_()`` on those, and on
+        no other; ``state.learnables``), the configured scheduler and early stopping.  A ``ValueError`` for a choice that cannot
+        be learned (the class docstring).  None for a group without samples."""
         from .optim import Adam
         device = _gpu_device(device)
+        if "translation_deviations" in self.parameters and not self._flux_driven:
+            raise ValueError("'translation_deviations' cannot be learned with reconstruction_method='alignment': the predicted "
+                             "normal is the third column of the orientation, translations do not enter it, and their gradient "
+                             "is identically zero; use the flux-driven method ('raytracing') or leave them out")
         group = self.scenario.heliostat_field.heliostat_groups[heliostat_group_index]
+        if "actuator_parameters" in self.parameters and group.kinematics.actuators.optimizable_parameters.numel() == 0:
+            raise ValueError(f"'actuator_parameters' cannot be learned on heliostat group {heliostat_group_index}: its actuators "
+                             f"are ideal, actuators.optimizable_parameters is empty")
         flux_measured, focal_spots, incident, motor_positions, mask, targets = self.data["data_parser"].parse_data_for_reconstruction(
             heliostat_data_mapping=self.data["heliostat_data_mapping"], heliostat_group=group, scenario=self.scenario,
             bitmap_resolution=self.bitmap_resolution, device=device)
@@ -159,14 +210,19 @@ class KinematicsReconstructor:
                                           incident_ray_directions=incident, motor_positions=motor_positions,
                                           target_area_indices=targets, device=device)
         kinematics = group.kinematics
-        optimizer = Adam([kinematics.rotation_deviation_parameters.requires_grad_()],
+        rates = learning_rates(self.optimizer_dict, self.parameters, KINEMATICS_LEARNING_RATE_KEYS)
+        learnables = {}
+        for name in self.parameters:
+            holder, attribute, _ = _slot(kinematics, name)
+            learnables[name] = getattr(holder, attribute)
+        optimizer = Adam([dict(params=[tensor.requires_grad_()], lr=rates[name]) for name, tensor in learnables.items()],
                          lr=float(self.optimizer_dict["initial_learning_rate_rotation_deviation"]))
         scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=optimizer, parameters=self.scheduler_dict)
         stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
                                          patience=self.optimizer_dict["early_stopping_patience"],
                                          min_improvement=self.optimizer_dict["early_stopping_delta"], relative=True)
         state = KinematicsGroupState(index=heliostat_group_index, group=group, mask=mask, split=split, active_rows=active_rows,
-                                     optimizer=optimizer, scheduler=scheduler, early_stopper=stopper)
+                                     optimizer=optimizer, scheduler=scheduler, early_stopper=stopper, learnables=learnables)
         if not self._flux_driven:
             state.normals_measured = self._compute_measured_normals(group, focal_spots, incident, mask, device)
             state.normals_measured_train = state.normals_measured[split.train_indices.to(device)]
@@ -210,9 +266,9 @@ class KinematicsReconstructor:
         return state.own.lookup(per_sample, lambda: per_sample.index_select(0, sample_rows), key="train")
 
     def _orientations(self, state: KinematicsGroupState, kind: str, device) -> torch.Tensor:
-        """Rotation deviations -> the orientations of the samples of ``kind``, ``[samples, 4, 4]`` (:506-514, 568-577).  The
-        group is activated for ``kind`` when it is not; the deviations of the heliostats that have samples are taken once and
-        expanded over the sample axis with a view."""
+        """The learned tensors -> the orientations of the samples of ``kind``, ``[samples, 4, 4]`` (:506-514, 568-577).  The
+        group is activated for ``kind`` when it is not; of every learned tensor the rows of the heliostats that have samples
+        are taken once and expanded over the sample axis with a view."""
         group, split = state.group, state.split
         train = kind == "train"
         mask = split.active_heliostats_mask_train if train else split.active_heliostats_mask_test
@@ -223,10 +279,12 @@ class KinematicsReconstructor:
             state.surfaces = (group.active_surface_points, group.active_surface_normals)
             state.activated = kind
         kinematics = group.kinematics
-        rows = kinematics.rotation_deviation_parameters.index_select(0, state.active_rows)
-        active = rows.shape[0]
-        kinematics.active_rotation_deviation_parameters = rows.reshape(active, 1, 4).expand(-1, samples, -1).reshape(
-            active * samples, 4)                                 # backward: .sum(1) over the samples, a fixed order
+        for name, tensor in state.learnables.items():            # (a tensor that does not learn keeps the activation's copy)
+            holder, _, active_attribute = _slot(kinematics, name)
+            rows = tensor.index_select(0, state.active_rows)
+            active, shape = rows.shape[0], rows.shape[1:]
+            setattr(holder, active_attribute, rows.reshape(active, 1, *shape).expand(active, samples, *shape).reshape(
+                active * samples, *shape))                       # backward: .sum(1) over the samples, a fixed order
         return kinematics.motor_positions_to_orientations(
             motor_positions=split.motor_positions_train if train else split.motor_positions_test, device=device)
 
@@ -300,7 +358,7 @@ class KinematicsReconstructor:
     def build_epoch_graph(self, state: KinematicsGroupState, loss_definition, device: torch.device | None = None):
         """The group's training step - :meth:`epoch_loss` and ``backward()`` - as an ``artist_amd.EpochGraph`` (``state.graph``),
         built after :meth:`prepare` and before the deviations' first use.  ``replay()`` leaves the gradient on
-        ``rotation_deviation_parameters`` and returns ``(total loss, loss per heliostat, loss per sample)``, detached, the bits
+        every learned tensor (``state.learnables``) and returns ``(total loss, loss per heliostat, loss per sample)``, detached, the bits
         of the eager step.
 
         The warm-up runs make what an eager first epoch makes - the activation for the training samples and, flux-driven, the
@@ -311,7 +369,6 @@ class KinematicsReconstructor:
         for training again after a validation.  :meth:`close_epoch_graph` ends it."""
         from . import graphs
         device = _gpu_device(device)
-        parameter = state.optimizer.param_groups[0]["params"][0]
 
         def step():
             loss = self.epoch_loss(state, loss_definition, device)
@@ -319,7 +376,7 @@ class KinematicsReconstructor:
             return loss.total.detach(), loss.per_heliostat.detach(), loss.per_sample.detach()
 
         try:
-            state.graph = graphs.EpochGraph(step, warmup=2, parameters=[parameter], device=device)
+            state.graph = graphs.EpochGraph(step, warmup=2, parameters=list(state.learnables.values()), device=device)
         except BaseException:
             self.close_epoch_graph(state)
             raise
@@ -335,7 +392,9 @@ class KinematicsReconstructor:
         state.graph, state.kept = None, []
         group, kinematics = state.group, state.group.kinematics
         group.active_surface_points, group.active_surface_normals = group.active_surface_points.detach(), group.active_surface_normals.detach()
-        kinematics.active_rotation_deviation_parameters = kinematics.active_rotation_deviation_parameters.detach()
+        for name in state.learnables:
+            holder, _, active_attribute = _slot(kinematics, name)
+            setattr(holder, active_attribute, getattr(holder, active_attribute).detach())
 
     def _synchronize_gradients_nested_ddp(self, optimizer: torch.optim.Optimizer) -> None:
         """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
@@ -350,7 +409,8 @@ class KinematicsReconstructor:
                     parameter.grad /= ddp["heliostat_group_world_size"]
 
     def _synchronize_reconstruction_across_ranks(self, final_loss_per_heliostat: torch.Tensor, loss_history: list) -> list:
-        """Every group's rotation deviations and optimisable actuator parameters from the first rank that owns the group, the
+        """Every group's rotation deviations and optimisable actuator parameters - and its translation deviations when they
+        are learned - from the first rank that owns the group, the
         final losses MIN-reduced (a heliostat another rank reconstructed is ``inf`` here), the histories of all ranks gathered
         (:650-705).  Returns the histories per rank; ``[loss_history]`` in a single process."""
         ddp = self.ddp_setup
@@ -360,6 +420,8 @@ class KinematicsReconstructor:
             for index, group in enumerate(self.scenario.heliostat_field.heliostat_groups):
                 source = ddp["ranks_to_groups_mapping"][index][0]
                 torch.distributed.broadcast(group.kinematics.rotation_deviation_parameters.detach(), src=source)
+                if "translation_deviations" in self.parameters:
+                    torch.distributed.broadcast(group.kinematics.translation_deviation_parameters.detach(), src=source)
                 torch.distributed.broadcast(group.kinematics.actuators.optimizable_parameters.detach(), src=source)
         torch.distributed.all_reduce(final_loss_per_heliostat, op=torch.distributed.ReduceOp.MIN)
         histories: list = [[] for _ in range(ddp["world_size"])]
@@ -368,14 +430,14 @@ class KinematicsReconstructor:
         return histories
 
     def reconstruct_kinematics(self, loss_definition, device: torch.device | None = None):
-        """Reconstruct the rotation deviations of the groups this rank owns (:707-884 alignment-driven, :886-1063
+        """Reconstruct the rotation deviations (or what ``self.parameters`` names) of the groups this rank owns (:707-884 alignment-driven, :886-1063
         flux-driven).  Returns ``(final loss per heliostat of the scenario on the CPU, +inf where a heliostat was not
         reconstructed; the histories: one list per rank, one entry per group)``; an entry is ``{"total_loss": a float per epoch,
         "test_loss": the last validation's {"pixel_loss", "kl_div", "focal_spot_loss"} per heliostat}``.  A group runs while its
         loss is above ``tolerance`` and ``epoch <= max_epoch``, or until early stopping, which ends the group before that
         epoch's history entry.  The flux-driven mode averages the gradients over a group's sub-world and synchronises the
         ranks afterwards; the alignment-driven mode issues no collective, as in the reference, and returns this rank's
-        histories alone.  The parameters are detached at the end."""
+        histories alone.  The learned tensors are detached at the end."""
         device = _gpu_device(device)
         ddp = self.ddp_setup
         rank = ddp["rank"]
@@ -393,7 +455,6 @@ class KinematicsReconstructor:
             if state is None:                                        # a group without samples
                 continue
             optimizer, scheduler = state.optimizer, state.scheduler
-            parameter = optimizer.param_groups[0]["params"][0]
             total_loss: list[float] = []
             test_loss = None
             loss_host = float("inf")
@@ -412,7 +473,8 @@ class KinematicsReconstructor:
                         self._synchronize_gradients_nested_ddp(optimizer)
                     else:
                         # a sample whose normals are parallel has a non-finite gradient: it does not take part in the epoch
-                        parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
+                        for parameter in state.learnables.values():
+                            parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
                     optimizer.step()
                     loss_host = total.item()                             # the epoch's one read, after the step has been queued
                     if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
@@ -441,5 +503,7 @@ class KinematicsReconstructor:
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history) if self._flux_driven \
             else [loss_history]
         for group in groups:
-            group.kinematics.rotation_deviation_parameters = group.kinematics.rotation_deviation_parameters.detach()
+            for name in self.parameters:
+                holder, attribute, _ = _slot(group.kinematics, name)
+                setattr(holder, attribute, getattr(holder, attribute).detach())
         return final_loss_per_heliostat.detach().cpu(), histories

@@ -10,7 +10,8 @@ The update rule is ``torch.optim.adam._single_tensor_adam`` in fp32; tests compa
 reference has them (``artist.optim``), and so are ``AimPointOptimizer`` (``artist_amd.aim_point_optimizer``),
 ``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``; with ``parameters=(...)`` it hands this ``Adam`` one parameter
 group per learnable tensor - control points, facet canting, facet translations), ``KinematicsReconstructor``
-(``artist_amd.kinematics_reconstructor``) and the losses on vectors it compares normals with (``artist_amd.losses``).
+(``artist_amd.kinematics_reconstructor``; with ``parameters=(...)``, drawn from ``KINEMATICS_PARAMETER_NAMES``, one parameter
+group per learnable tensor as well - rotation deviations, translation deviations, actuator parameters) and the losses on vectors it compares normals with (``artist_amd.losses``).
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ from .losses import AngleLoss, CosineSimilarityLoss, VectorLoss
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer
 
 __all__ = ["Adam", "AimPointOptimizer", "SurfaceReconstructor", "KinematicsReconstructor", "SmoothnessRegularizer",
-           "IdealSurfaceRegularizer", "VectorLoss", "AngleLoss", "CosineSimilarityLoss"]
+           "IdealSurfaceRegularizer", "VectorLoss", "AngleLoss", "CosineSimilarityLoss", "KINEMATICS_PARAMETER_NAMES"]
 
 
 class Adam(torch.optim.Optimizer):
@@ -83,4 +84,4 @@ class Adam(torch.optim.Optimizer):
 
 from .aim_point_optimizer import AimPointOptimizer  # noqa: E402  (it steps with the Adam above)
 from .surface_reconstructor import SurfaceReconstructor  # noqa: E402  (and so does this one)
-from .kinematics_reconstructor import KinematicsReconstructor  # noqa: E402  (and this one)
+from .kinematics_reconstructor import KINEMATICS_PARAMETER_NAMES, KinematicsReconstructor  # noqa: E402  (and this one)

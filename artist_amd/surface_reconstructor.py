@@ -51,7 +51,7 @@ from .training import reduce_loss_per_sample
 log = logging.getLogger(__name__)
 
 __all__ = ["SurfaceReconstructor", "CalibrationSamples", "GroupState", "EpochLoss", "flux_integral_constraint", "HISTORY_KEYS",
-           "PARAMETER_NAMES", "canonical_parameters", "learning_rates", "tensors_held_by"]
+           "PARAMETER_NAMES", "LEARNING_RATE_KEYS", "canonical_parameters", "learning_rates", "tensors_held_by", "LearnsParameters"]
 
 #: the per-epoch lists of a group's history, in the order the epoch's scalars are stacked; ``"test_loss"`` comes on top
 HISTORY_KEYS = ("total_loss", "flux_loss", "smoothness_regularizer", "ideal_regularizer", "flux_integral",
@@ -64,27 +64,34 @@ PARAMETER_NAMES = ("nurbs_control_points", "canting", "facet_translations")
 _mean_over_samples = partial(torch.mean, dim=-1)
 
 
-def canonical_parameters(parameters) -> tuple:
-    """``parameters`` - a non-empty tuple or list of ``PARAMETER_NAMES``, in any order, duplicates allowed - as a tuple in the
-    canonical order.  Anything else is a ``ValueError`` that lists the three names."""
-    allowed = ", ".join(repr(name) for name in PARAMETER_NAMES)
+#: the configuration key of every name's initial learning rate; the first is required and the default of the others
+LEARNING_RATE_KEYS = {"nurbs_control_points": "initial_learning_rate", "canting": "initial_learning_rate_canting",
+                      "facet_translations": "initial_learning_rate_facet_translations"}
+
+
+def canonical_parameters(parameters, names=PARAMETER_NAMES) -> tuple:
+    """``parameters`` - a non-empty tuple or list of ``names`` (a reconstructor's parameter names in their canonical order;
+    the surface reconstructor's by default), in any order, duplicates allowed - as a tuple in the canonical order.  Anything
+    else is a ``ValueError`` that lists the names."""
+    allowed = ", ".join(repr(name) for name in names)
     if not isinstance(parameters, (tuple, list)) or len(parameters) == 0:
         raise ValueError(f"parameters must be a non-empty tuple or list drawn from {allowed}; got {parameters!r}")
-    unknown = [name for name in parameters if name not in PARAMETER_NAMES]
+    unknown = [name for name in parameters if name not in names]
     if unknown:
         raise ValueError(f"unknown parameter(s) {unknown!r}: parameters must be drawn from {allowed}")
-    return tuple(name for name in PARAMETER_NAMES if name in parameters)
+    return tuple(name for name in names if name in parameters)
 
 
-def learning_rates(optimizer_dict: dict, parameters=PARAMETER_NAMES) -> dict:
-    """The initial learning rate of every name in ``parameters``, in the canonical order, from the configuration's
-    ``"optimization"`` table: ``"initial_learning_rate"`` for the control points, the optional
-    ``"initial_learning_rate_canting"`` and ``"initial_learning_rate_facet_translations"`` for the two rigid tensors, each
-    defaulting to ``"initial_learning_rate"``."""
-    default = float(optimizer_dict["initial_learning_rate"])
-    keys = {"nurbs_control_points": "initial_learning_rate", "canting": "initial_learning_rate_canting",
-            "facet_translations": "initial_learning_rate_facet_translations"}
-    return {name: float(optimizer_dict.get(keys[name], default)) for name in canonical_parameters(parameters)}
+def learning_rates(optimizer_dict: dict, parameters=None, keys=LEARNING_RATE_KEYS) -> dict:
+    """The initial learning rate of every name in ``parameters`` (all of ``keys`` by default), in the canonical order, from
+    the configuration's ``"optimization"`` table.  ``keys`` maps a reconstructor's parameter names, in their canonical order,
+    to their configuration keys; the first key is required, the others are optional and default to it.  For the surface
+    reconstructor (the default): ``"initial_learning_rate"`` for the control points, ``"initial_learning_rate_canting"`` and
+    ``"initial_learning_rate_facet_translations"`` for the two rigid tensors."""
+    names = tuple(keys)
+    default = float(optimizer_dict[keys[names[0]]])
+    return {name: float(optimizer_dict.get(keys[name], default))
+            for name in canonical_parameters(names if parameters is None else parameters, names)}
 
 
 def flux_integral_constraint(cropped_sums: torch.Tensor, reference: torch.Tensor, multiplier, rho: float, energy_tolerance: float,
@@ -210,16 +217,36 @@ class _TakesParameters(type):
     """``SurfaceReconstructor(..., epoch_graph=False, parameters=(...))``: the class call takes the one keyword that the
     reference's constructor has no place for, checks it before ``__init__`` runs - so before any device work - and sets the
     attribute.  ``__init__`` itself keeps the signature both reconstructors share, the reference's arguments and then
-    ``epoch_graph`` (tests/test_reconstructor_graphs_host.py holds it to that)."""
+    ``epoch_graph`` (tests/test_reconstructor_graphs_host.py holds it to that).  ``KinematicsReconstructor`` takes its
+    keyword the same way: the class's ``PARAMETER_NAMES`` are the names it draws from, the first of them the default."""
 
-    def __call__(cls, *args, parameters=("nurbs_control_points",), **kwargs):
-        chosen = canonical_parameters(parameters)
+    _first = object()       # (the keyword left out; None is a wrong value like any other)
+
+    def __call__(cls, *args, parameters=_first, **kwargs):
+        names = cls.PARAMETER_NAMES
+        chosen = canonical_parameters(names[:1] if parameters is _TakesParameters._first else parameters, names)
         reconstructor = super().__call__(*args, **kwargs)
         reconstructor.parameters = chosen
         return reconstructor
 
 
-class SurfaceReconstructor(metaclass=_TakesParameters):
+class LearnsParameters(metaclass=_TakesParameters):
+    """What the reconstructors share of the keyword: the attribute ``parameters``, checked and ordered on assignment against
+    the class's ``PARAMETER_NAMES``; the first name alone unless chosen otherwise."""
+    PARAMETER_NAMES: tuple = ()
+    _parameters = None
+
+    @property
+    def parameters(self) -> tuple:
+        """What learns, in the canonical order (``PARAMETER_NAMES``)."""
+        return type(self).PARAMETER_NAMES[:1] if self._parameters is None else self._parameters
+
+    @parameters.setter
+    def parameters(self, parameters) -> None:
+        self._parameters = canonical_parameters(parameters, type(self).PARAMETER_NAMES)
+
+
+class SurfaceReconstructor(LearnsParameters):
     """``artist.optim.SurfaceReconstructor``: see the module docstring; attributes as in the reference (:58-84).
 
     ``prepare`` / ``predict_flux`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_surfaces`` runs per group, for
@@ -275,16 +302,7 @@ class SurfaceReconstructor(metaclass=_TakesParameters):
         self.validation_loss_pixel = PixelLoss()
         self.validation_loss_kl_div = KLDivergenceLoss()
 
-    _parameters = PARAMETER_NAMES[:1]           # the control points alone, unless chosen otherwise
-
-    @property
-    def parameters(self) -> tuple:
-        """What learns, in the canonical order (``PARAMETER_NAMES``)."""
-        return self._parameters
-
-    @parameters.setter
-    def parameters(self, parameters) -> None:
-        self._parameters = canonical_parameters(parameters)
+    PARAMETER_NAMES = PARAMETER_NAMES           # (the control points alone, unless chosen otherwise)
 
     # ------------------------------------------------------------------------------------------
     def prepare(self, heliostat_group_index: int, device: torch.device | None = None) -> GroupState | None:

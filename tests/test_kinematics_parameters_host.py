@@ -1,0 +1,248 @@
+"""``KinematicsReconstructor(parameters=...)`` without a GPU: the keyword's validation, the refusals of ``prepare``, the
+learning-rate defaults, the consistency of tests/golden/kinematics_parameters_flux.npz and ``..._alignment.npz``
+(tests/golden/generate_kinematics_parameters_golden.py) with what the GPU tests take from them, one Adam step in fp64 from a
+recorded gradient, and - two gloo processes on CPU tensors - the broadcast of the translation deviations at the end of a run."""
+import json
+import os
+import socket
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+FLUX, ALIGNMENT = "kinematics_parameters_flux", "kinematics_parameters_alignment"
+NAMES = ("rotation_deviations", "translation_deviations", "actuator_parameters")
+LEARNED = {FLUX: NAMES, ALIGNMENT: ("rotation_deviations", "actuator_parameters")}
+RATE_KEYS = ("initial_learning_rate_rotation_deviation", "initial_learning_rate_translation_deviation",
+             "initial_learning_rate_actuator_parameters")
+DDP = dict(rank=0, world_size=1, is_distributed=False, is_nested=False, process_subgroup=None, groups_to_ranks_mapping={0: [0]},
+           ranks_to_groups_mapping={0: [0]}, heliostat_group_rank=0, heliostat_group_world_size=1)
+CONFIGURATION = dict(optimization={}, scheduler={})
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def _make(ddp=DDP, scenario=None, method="raytracing", device=torch.device("cuda", 0), **kwargs):
+    from artist_amd.optim import KinematicsReconstructor
+    return KinematicsReconstructor(ddp_setup=ddp, scenario=scenario, data={}, optimization_configuration=CONFIGURATION,
+                                   reconstruction_method=method, device=device, **kwargs)    # (nothing here touches the device)
+
+
+def test_the_names_are_exported():
+    from artist_amd import kinematics_reconstructor, optim, surface_reconstructor
+    assert kinematics_reconstructor.KINEMATICS_PARAMETER_NAMES == NAMES == optim.KINEMATICS_PARAMETER_NAMES
+    assert "KINEMATICS_PARAMETER_NAMES" in kinematics_reconstructor.__all__ and "KINEMATICS_PARAMETER_NAMES" in optim.__all__
+    assert optim.KinematicsReconstructor.PARAMETER_NAMES == NAMES
+    assert tuple(kinematics_reconstructor.KINEMATICS_LEARNING_RATE_KEYS) == NAMES
+    assert tuple(kinematics_reconstructor.KINEMATICS_LEARNING_RATE_KEYS.values()) == RATE_KEYS
+    # one helper for both reconstructors
+    assert kinematics_reconstructor.learning_rates is surface_reconstructor.learning_rates
+    assert issubclass(optim.KinematicsReconstructor, surface_reconstructor.LearnsParameters)
+    assert issubclass(optim.SurfaceReconstructor, surface_reconstructor.LearnsParameters)
+
+
+def test_the_keyword_is_checked_in_the_constructor():
+    assert _make().parameters == ("rotation_deviations",)
+    assert _make(epoch_graph=True, parameters=["actuator_parameters"]).parameters == ("actuator_parameters",)
+    assert _make(parameters=("actuator_parameters", "rotation_deviations")).parameters == ("rotation_deviations", "actuator_parameters")
+    assert _make(parameters=["translation_deviations", "actuator_parameters", "translation_deviations", "rotation_deviations"]).parameters == NAMES
+    assert _make(method="alignment", parameters=NAMES).parameters == NAMES            # (refused in prepare, where the reason shows)
+    for wrong in ((), [], ("rotations",), ("rotation_deviations", "canting"), ("nurbs_control_points",), "rotation_deviations", None, (None,)):
+        with pytest.raises(ValueError) as raised:
+            _make(parameters=wrong)
+        assert all(name in str(raised.value) for name in NAMES), str(raised.value)
+        assert "facet_translations" not in str(raised.value)                            # ... and not the surface reconstructor's
+    reconstructor = _make()
+    reconstructor.parameters = ["actuator_parameters", "translation_deviations"]
+    assert reconstructor.parameters == ("translation_deviations", "actuator_parameters")
+    with pytest.raises(ValueError):
+        reconstructor.parameters = ("canting",)
+    assert reconstructor.parameters == ("translation_deviations", "actuator_parameters")
+    # __init__ keeps the signature both reconstructors share
+    import inspect
+    assert list(inspect.signature(type(reconstructor).__init__).parameters)[-1] == "epoch_graph"
+    # the names are checked before any device work: a CPU device is refused only after them
+    from artist_amd import ArtistHipError
+    with pytest.raises(ValueError):
+        _make(device=torch.device("cpu"), parameters=("tilt",))
+    with pytest.raises(ArtistHipError, match="no CPU fallback"):
+        _make(device=torch.device("cpu"), parameters=("actuator_parameters",))
+    # the surface reconstructor's own names and default are as they were
+    from artist_amd.optim import SurfaceReconstructor
+    surface = SurfaceReconstructor(ddp_setup=DDP, scenario=None, data={}, optimization_configuration=dict(optimization={}, scheduler={}, constraints={}),
+                                   device=torch.device("cuda", 0))
+    assert surface.parameters == ("nurbs_control_points",)
+    with pytest.raises(ValueError, match="nurbs_control_points"):
+        surface.parameters = ("rotation_deviations",)
+
+
+def _scenario(optimizable):
+    actuators = types.SimpleNamespace(optimizable_parameters=optimizable)
+    kinematics = types.SimpleNamespace(rotation_deviation_parameters=torch.zeros(2, 4), translation_deviation_parameters=torch.zeros(2, 9),
+                                       actuators=actuators)
+    group = types.SimpleNamespace(kinematics=kinematics, number_of_heliostats=2)
+    return types.SimpleNamespace(heliostat_field=types.SimpleNamespace(heliostat_groups=[group]))
+
+
+def test_prepare_refuses_what_cannot_be_learned():
+    """Both refusals come before the calibration data is asked for (``data`` is empty here) and before any device work."""
+    linear, ideal = torch.zeros(2, 2, 2), torch.tensor([])
+    for parameters in (("translation_deviations",), NAMES):
+        with pytest.raises(ValueError, match="translation_deviations.*alignment.*do not enter.*identically zero"):
+            _make(scenario=_scenario(linear), method="alignment", parameters=parameters).prepare(0, torch.device("cuda", 0))
+    for method in ("raytracing", "alignment"):
+        with pytest.raises(ValueError, match="actuator_parameters.*group 0.*ideal.*optimizable_parameters is empty"):
+            _make(scenario=_scenario(ideal), method=method, parameters=("rotation_deviations", "actuator_parameters")).prepare(
+                0, torch.device("cuda", 0))
+    # what is allowed gets past both and asks for the data
+    for method, parameters, scenario in (("raytracing", NAMES, _scenario(linear)), ("alignment", NAMES[::2], _scenario(linear)),
+                                         ("raytracing", NAMES[:2], _scenario(ideal)), ("alignment", NAMES[:1], _scenario(ideal))):
+        with pytest.raises(KeyError, match="data_parser"):
+            _make(scenario=scenario, method=method, parameters=parameters).prepare(0, torch.device("cuda", 0))
+        kinematics = scenario.heliostat_field.heliostat_groups[0].kinematics
+        assert not kinematics.translation_deviation_parameters.requires_grad and not kinematics.actuators.optimizable_parameters.requires_grad
+
+
+def test_the_learning_rates_default_to_the_rotation_deviations():
+    from artist_amd.kinematics_reconstructor import KINEMATICS_LEARNING_RATE_KEYS as keys
+    from artist_amd.surface_reconstructor import learning_rates
+    assert learning_rates({RATE_KEYS[0]: 2e-4}, keys=keys) == dict.fromkeys(NAMES, 2e-4)
+    assert list(learning_rates({RATE_KEYS[0]: 2e-4}, keys=keys)) == list(NAMES)
+    every = {RATE_KEYS[0]: "2e-4", RATE_KEYS[1]: 1e-4, RATE_KEYS[2]: 5e-5}
+    assert learning_rates(every, NAMES, keys) == {"rotation_deviations": 2e-4, "translation_deviations": 1e-4, "actuator_parameters": 5e-5}
+    assert learning_rates(every, ("actuator_parameters", "translation_deviations"), keys) == {"translation_deviations": 1e-4,
+                                                                                              "actuator_parameters": 5e-5}
+    assert learning_rates({RATE_KEYS[0]: 1e-3, RATE_KEYS[2]: 0.0}, ["actuator_parameters"], keys) == {"actuator_parameters": 0.0}
+    assert learning_rates({RATE_KEYS[0]: 1e-3, RATE_KEYS[2]: 3e-3}, NAMES[:2], keys) == {"rotation_deviations": 1e-3, "translation_deviations": 1e-3}
+    with pytest.raises(ValueError):
+        learning_rates({RATE_KEYS[0]: 1e-3}, ("canting",), keys)
+    with pytest.raises(KeyError):                      # the rotation key stays required, also when the rotations do not learn
+        learning_rates({RATE_KEYS[2]: 1e-3}, ("actuator_parameters",), keys)
+    # the surface reconstructor's table is the default, as before
+    assert learning_rates({"initial_learning_rate": 2e-5, "initial_learning_rate_canting": 5e-5}, ("canting",)) == {"canting": 5e-5}
+
+
+@pytest.mark.parametrize("name", [FLUX, ALIGNMENT])
+def test_the_fixture_is_consistent(golden, name):
+    d = golden(name)
+    learned = LEARNED[name]
+    assert tuple(d["learned"].tolist()) == learned and str(d["method"]) == ("raytracing" if name == FLUX else "alignment")
+    mask = d["parser_mask"]
+    active, inactive = np.nonzero(mask)[0], np.nonzero(mask == 0)[0]
+    assert mask.tolist() == [4, 0, 4, 0, 4, 4] and tuple(d["split_counts"]) == (3, 1, 4)
+    assert d["points_per_facet"].tolist() == [10, 10] and int(d["n_rays"]) == 3 and d["resolution"].tolist() == [64, 64]
+    configuration = json.loads(str(d["configuration"]))
+    optimization = configuration["optimization"]
+    assert optimization["max_epoch"] == 2 and optimization["log_step"] == 1 and d["validated_epochs"].tolist() == [0, 1, 2]
+    # a rate of its own per group, all following the exponential schedule
+    initial = [optimization[RATE_KEYS[NAMES.index(tensor)]] for tensor in learned]
+    assert len(set(initial)) == len(learned) and d["lr"].shape == (3, len(learned))
+    np.testing.assert_allclose(d["lr"], np.asarray(initial)[None] * configuration["scheduler"]["gamma"] ** np.arange(3)[:, None], rtol=1e-12)
+    shapes = {"rotation_deviations": (6, 4), "translation_deviations": (6, 9), "actuator_parameters": (6, 2, 2)}
+    for tensor in NAMES[1:]:                            # the extra tensors start perturbed in every run
+        assert d[f"initial_{tensor}"].shape == shapes[tensor] and (d[f"initial_{tensor}"] != d[f"true_{tensor}"]).all()
+        assert np.abs(d[f"initial_{tensor}"] - d[f"true_{tensor}"]).max() < 5 * float(d[f"sigma_{tensor}"])
+    for tensor in learned:
+        start, grad, after = d[f"start_{tensor}"], d[f"grad_{tensor}"], d[f"after_{tensor}"]
+        assert start.shape == grad.shape == after.shape == (3,) + shapes[tensor] == d[f"after_{tensor}_f64"].shape
+        assert d[f"grad_{tensor}_f64_epoch0"].shape == shapes[tensor]
+        assert np.isfinite(grad).all() and np.isfinite(d[f"grad_{tensor}_f64_epoch0"]).all()
+        np.testing.assert_array_equal(after[:-1], start[1:])
+        assert not grad[:, inactive].any() and not d[f"grad_{tensor}_f64_epoch0"][inactive].any()       # no sample, no gradient,
+        np.testing.assert_array_equal(after[:, inactive], start[:, inactive])                           # no step
+        assert (grad[:, active] != 0).all(), tensor                                                     # no column without one
+        assert not np.array_equal(after[-1][active], start[0][active])
+        if tensor != "rotation_deviations":
+            np.testing.assert_array_equal(start[0], d[f"initial_{tensor}"])
+    np.testing.assert_array_equal(d["start_rotation_deviations"][0], d["rotation_start"][0])
+    assert "start_translation_deviations" in d if name == FLUX else "start_translation_deviations" not in d
+    assert np.isinf(d["final_loss"][inactive]).all() and np.array_equal(d["final_loss"][active], d["loss_per_heliostat"][-1])
+    np.testing.assert_allclose(d["loss_per_heliostat"].astype(np.float64).mean(axis=1), d["total_loss"], rtol=1e-6)
+    per_sample = d["loss_per_sample"].astype(np.float64)
+    distance = np.abs(per_sample[0] - d["loss_per_sample_f64_epoch0"])
+    if name == FLUX:        # every heliostat's median sample stands clear of its neighbours: fp32 and fp64 pick the same one
+        blocks = np.sort(per_sample.reshape(3, 4, 3), axis=2)
+        np.testing.assert_array_equal(blocks[..., 1].astype(np.float32), d["loss_per_heliostat"])
+        gap = np.minimum(blocks[..., 1] - blocks[..., 0], blocks[..., 2] - blocks[..., 1])
+        assert (gap >= 10 * distance.max()).all(), (gap.min(), distance.max())
+        assert d["flux_predicted"].shape == (3, 12, 64, 64) and int(d["seed_train"]) == 0 and int(d["seed_test"]) == 7
+    else:
+        assert (distance / np.abs(d["loss_per_sample_f64_epoch0"])).max() < 1e-2
+        np.testing.assert_allclose(per_sample.reshape(3, 4, 3).mean(axis=2), d["loss_per_heliostat"], rtol=1e-6)
+        assert d["normals_predicted"].shape == (3, 12, 4) and "distortions_train_u" not in d
+
+
+@pytest.mark.parametrize("name", [FLUX, ALIGNMENT])
+def test_adam_in_fp64_lands_on_the_recorded_values(golden, name):
+    """``torch.optim.Adam`` in fp64, one parameter group per tensor at the recorded rates, fed the recorded (fp32) gradients from
+    the recorded start: after every step it lands on the recorded fp32 value.  The recorded update was formed in fp32 - the
+    two moments, a square root, a quotient: a relative error of a few ulp on a step of at most about one learning rate (the
+    bias-corrected quotient of the moments is at most 1 in the first steps but for rounding) - and added to the value, which
+    rounds once more: ``8 ulp x lr + 1 ulp of the value`` per step; the steps before add theirs to the start of the next."""
+    d = golden(name)
+    learned = LEARNED[name]
+    leaves = [torch.from_numpy(d[f"start_{tensor}"][0].astype(np.float64)).requires_grad_() for tensor in learned]
+    optimizer = torch.optim.Adam([dict(params=[leaf], lr=float(lr)) for leaf, lr in zip(leaves, d["lr"][0])])
+    scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=json.loads(str(d["configuration"]))["scheduler"]["gamma"])
+    for e in range(3):
+        np.testing.assert_allclose([group["lr"] for group in optimizer.param_groups], d["lr"][e], rtol=1e-12)
+        for leaf, tensor in zip(leaves, learned):
+            leaf.grad = torch.from_numpy(d[f"grad_{tensor}"][e].astype(np.float64))
+        optimizer.step()
+        scheduler.step()
+        for leaf, tensor, lr in zip(leaves, learned, d["lr"][e]):
+            recorded = d[f"after_{tensor}"][e].astype(np.float64)
+            bound = (e + 1) * (8 * EPS32 * lr + EPS32 * np.abs(recorded))
+            assert (np.abs(leaf.detach().numpy() - recorded) <= bound).all(), (e, tensor, np.abs(leaf.detach().numpy() - recorded).max())
+            # ... which is not where the step started: the bound is a small part of the step
+            assert np.abs(recorded - d[f"start_{tensor}"][e]).max() > 0.5 * lr > 10 * bound.max()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _group(count, value):
+    actuators = types.SimpleNamespace(optimizable_parameters=torch.full((count, 2, 2), value + 0.5))
+    kinematics = types.SimpleNamespace(rotation_deviation_parameters=torch.full((count, 4), value).requires_grad_(),
+                                       translation_deviation_parameters=torch.full((count, 9), value + 0.25), actuators=actuators)
+    return types.SimpleNamespace(kinematics=kinematics, number_of_heliostats=count)
+
+
+def _worker(rank, world, port, out_dir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        flat = dict(rank=rank, world_size=world, is_distributed=True, is_nested=False, process_subgroup=None,
+                    groups_to_ranks_mapping={0: [0]}, ranks_to_groups_mapping={0: [0]}, heliostat_group_rank=0, heliostat_group_world_size=1)
+        for parameters, learns in ((NAMES, True), (("translation_deviations",), True), (NAMES[::2], False), (None, False)):
+            group = _group(3, float(100 * rank))                   # rank 0 owns the group: 0, 0.25, 0.5; rank 1 holds 100, ...
+            if learns:
+                group.kinematics.translation_deviation_parameters.requires_grad_()
+            scenario = types.SimpleNamespace(heliostat_field=types.SimpleNamespace(heliostat_groups=[group]))
+            keyword = {} if parameters is None else dict(parameters=parameters)
+            reconstructor = _make(ddp=flat, scenario=scenario, **keyword)
+            final_loss = torch.full((3,), torch.inf if rank else 1.0)
+            histories = reconstructor._synchronize_reconstruction_across_ranks(final_loss, [dict(total_loss=[float(rank)])])
+            kinematics = group.kinematics
+            assert torch.equal(kinematics.rotation_deviation_parameters.detach(), torch.zeros(3, 4)), (rank, parameters)
+            assert torch.equal(kinematics.actuators.optimizable_parameters, torch.full((3, 2, 2), 0.5)), (rank, parameters)
+            own = 100.0 * rank + 0.25
+            assert torch.equal(kinematics.translation_deviation_parameters.detach(), torch.full((3, 9), 0.25 if learns else own)), (rank, parameters)
+            assert kinematics.translation_deviation_parameters.requires_grad == learns       # (written in place, not rebound)
+            assert final_loss.tolist() == [1.0] * 3 and [h[0]["total_loss"] for h in histories] == [[0.0], [1.0]]
+        (out_dir / f"ok_{rank}").write_text("ok")
+    finally:
+        dist.destroy_process_group()
+
+
+def test_the_translation_deviations_are_broadcast_when_they_learn(tmp_path):
+    """Two gloo processes at the end of a flux-driven run whose one group rank 0 owns: rank 1 holds rank 0's rotation deviations
+    and actuator table as before, and rank 0's translation deviations when they are learned; when they are not it keeps its own."""
+    mp.spawn(_worker, args=(2, _free_port(), tmp_path), nprocs=2, join=True)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["ok_0", "ok_1"]

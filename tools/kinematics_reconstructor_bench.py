@@ -17,7 +17,15 @@ loss; warm-up epochs come first and are not counted; every epoch's time is kept,
 the calls into the library per epoch by entry point (each is one kernel launch or a few), and the synchronising calls of one
 epoch, of an epoch with its validation and of the epoch after a validation, counted with ``torch.cuda.set_sync_debug_mode("warn")``.
 
+``--parameters a,b,...`` ("More kinematic parameters") measures something else: per size and mode the epoch that
+learns the rotation deviations alone beside the epoch that learns the given tensors (``KINEMATICS_PARAMETER_NAMES``), eager and
+replayed, all alternating in one process.  A name that a variant cannot learn is left out of that variant and said so
+(``left_out``): the translation deviations in the alignment-driven mode, the actuator parameters on the synthetic field's ideal
+actuators.  The fixture's two extra tensors keep the file's values.  Written to ``--out``, by default
+profiles/kinematics_parameters_bench.json.
+
 usage: python tools/kinematics_reconstructor_bench.py [--out profiles/kinematics_reconstructor_bench.json] [--epochs 30] [--blocks 3]
+                                                      [--parameters rotation_deviations,translation_deviations,actuator_parameters]
 """
 import argparse
 import collections
@@ -90,14 +98,15 @@ def synthetic_case(method, heliostats=100, samples=4, rays=10, n_eval=50, resolu
 
 
 class Epoch:
-    def __init__(self, method, case, epoch_graph=False):
+    def __init__(self, method, case, epoch_graph=False, parameters=None):
         from artist_amd import CalibrationSamples, FocalSpotLoss
         from artist_amd.optim import AngleLoss, KinematicsReconstructor
         scenario, six, resolution = case
         self.method = method
         self.reconstructor = KinematicsReconstructor(
             ddp_setup=DDP, scenario=scenario, data={"data_parser": CalibrationSamples(six), "heliostat_data_mapping": []},
-            optimization_configuration=CONFIGURATION, reconstruction_method=method, bitmap_resolution=resolution, device=DEV)
+            optimization_configuration=CONFIGURATION, reconstruction_method=method, bitmap_resolution=resolution, device=DEV,
+            **({} if parameters is None else dict(parameters=parameters)))
         self.loss_definition = FocalSpotLoss(scenario=scenario) if method == "raytracing" else AngleLoss()
         self.state = self.reconstructor.prepare(0, DEV)
         self.graph = None
@@ -118,7 +127,8 @@ class Epoch:
         else:
             total, _, _ = self.graph.replay()
         if self.method == "alignment":
-            state.optimizer.param_groups[0]["params"][0].grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
+            for group in state.optimizer.param_groups:
+                group["params"][0].grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
         state.optimizer.step()
         host = total.item()
         state.scheduler.step()
@@ -170,11 +180,29 @@ def count_calls(fn):
     return dict(sorted(calls.items()))
 
 
-def measure(name, make_case, epochs, blocks, warmup):
-    variants = {}
+def learnable(method, case, parameters):
+    """``parameters`` without what this mode on this field cannot learn: ``(what is left, {name: why it was left out})``."""
+    left_out = {}
+    if method == "alignment" and "translation_deviations" in parameters:
+        left_out["translation_deviations"] = "do not enter the predicted normal"
+    if "actuator_parameters" in parameters and case[0].heliostat_field.heliostat_groups[0].kinematics.actuators.optimizable_parameters.numel() == 0:
+        left_out["actuator_parameters"] = "ideal actuators"
+    return tuple(name for name in parameters if name not in left_out), left_out
+
+
+def measure(name, make_case, epochs, blocks, warmup, parameters=None):
+    variants, methods, left_out = {}, {}, {}
     for method in METHODS:                               # (each variant on a scenario of its own)
-        variants[method] = Epoch(method, make_case(method))
-        variants[f"{method}, epoch_graph"] = Epoch(method, make_case(method), epoch_graph=True)
+        choices = {method: None}
+        if parameters is not None:
+            chosen, left_out[method] = learnable(method, make_case(method), parameters)
+            choices = {f"{method}, rotation_deviations": ("rotation_deviations",)}
+            if chosen:                                   # (nothing left: the rotation deviations alone stand for the variant)
+                choices[f"{method}, {' + '.join(chosen)}"] = chosen
+        for key, choice in choices.items():
+            variants[key] = Epoch(method, make_case(method), parameters=choice)
+            variants[f"{key}, epoch_graph"] = Epoch(method, make_case(method), epoch_graph=True, parameters=choice)
+            methods[key] = method
     times = {key: [] for key in variants}
     for epoch in variants.values():
         for _ in range(warmup):
@@ -199,7 +227,7 @@ def measure(name, make_case, epochs, blocks, warmup):
         print(f"[{name}] {method}: median {v['median_ms']:.3f} ms (min {v['min_ms']:.3f}, p10 {v['p10_ms']:.3f}, p90 {v['p90_ms']:.3f}, "
               f"max {v['max_ms']:.3f}); library calls {v['library_calls_total']}: {calls}; synchronising calls {v['synchronising_calls']}",
               flush=True)
-    for method in METHODS:
+    for method in methods:
         e, g = result[method], result[f"{method}, epoch_graph"]
         g["eager_median_ms"], g["eager_over_replayed"] = e["median_ms"], e["median_ms"] / g["median_ms"]
         g["eager_p90_minus_p10_ms"] = e["p90_ms"] - e["p10_ms"]
@@ -208,23 +236,36 @@ def measure(name, make_case, epochs, blocks, warmup):
         g["build_in_eager_epochs"] = g["build_ms"] / e["median_ms"]
         print(f"[{name}] {method}, epoch_graph: eager / replayed {g['eager_over_replayed']:.2f}, build {g['build_ms']:.1f} ms = "
               f"{g['build_in_eager_epochs']:.1f} eager epochs, within the eager spread: {g['replay_within_eager_spread']}", flush=True)
+    if parameters is not None:
+        result["left_out"] = left_out
     return result
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "kinematics_reconstructor_bench.json"))
+    ap.add_argument("--out", default=None, help="profiles/kinematics_reconstructor_bench.json, with --parameters "
+                    "profiles/kinematics_parameters_bench.json")
+    ap.add_argument("--parameters", default=None, help="comma-separated KINEMATICS_PARAMETER_NAMES: measure the epoch that learns "
+                    "them beside the one that learns the rotation deviations alone")
     ap.add_argument("--epochs", type=int, default=30, help="timed epochs per block and mode")
     ap.add_argument("--blocks", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("kinematics_reconstructor_bench.py measures on the GPU; no GPU found")
+    parameters = None
+    if args.parameters is not None:
+        from artist_amd.kinematics_reconstructor import KINEMATICS_PARAMETER_NAMES
+        from artist_amd.surface_reconstructor import canonical_parameters
+        parameters = canonical_parameters([part.strip() for part in args.parameters.split(",") if part.strip()], KINEMATICS_PARAMETER_NAMES)
+    args.out = args.out or str(ROOT / "profiles" / ("kinematics_reconstructor_bench.json" if parameters is None else "kinematics_parameters_bench.json"))
     out = dict(device=torch.cuda.get_device_name(DEV), epochs_per_block=args.epochs, blocks=args.blocks, warmup=args.warmup,
                fixture=measure("fixture: 4 heliostats x 3 training samples, 400 points, 3 rays, 64 x 64", fixture_case, args.epochs,
-                               args.blocks, args.warmup),
+                               args.blocks, args.warmup, parameters),
                synthetic_100x4=measure("synthetic: 100 heliostats x 3 training samples, 10^4 points, 10 rays, 256 x 256", synthetic_case,
-                                       args.epochs, args.blocks, args.warmup))
+                                       args.epochs, args.blocks, args.warmup, parameters))
+    if parameters is not None:
+        out["parameters"] = list(parameters)
     pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     pathlib.Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
     print("wrote", args.out)
