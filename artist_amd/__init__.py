@@ -20,6 +20,7 @@ backward, behind ARTIST's own call surface:
     artist_amd.SmoothnessRegularizer, IdealSurfaceRegularizer
                                     <-> artist.optim.SmoothnessRegularizer, IdealSurfaceRegularizer (the epoch's regularisers)
     artist_amd.SurfaceGenerator     <-> artist.scenario.surface_generator.SurfaceGenerator (+ fit_nurbs_batch: all facets at once)
+    artist_amd.optics               (no counterpart) per-heliostat reflectivity, attenuation by slant range and optical error
     artist_amd.EpochGraph           (no counterpart) an epoch captured into a HIP graph and replayed: same bits, one host call
 
 All arithmetic runs in hand-written HIP kernels (``artist_amd/csrc``) reached through the C ABI in
@@ -32,7 +33,7 @@ from .flux import (FocalSpotLoss, KLDivergenceLoss, PixelLoss, bitmap_coordinate
                    trapezoid_distribution)
 from .kinematics import Actuators, RigidBody  # noqa: F401
 from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, perform_canting, trace_rays  # noqa: F401
-from . import optim, training  # noqa: F401
+from . import optics, optim, training  # noqa: F401
 from .aim_point_optimizer import AimPointOptimizer  # noqa: F401
 from .surface_reconstructor import CalibrationSamples, SurfaceReconstructor, flux_integral_constraint  # noqa: F401
 from .kinematics_reconstructor import KinematicsReconstructor  # noqa: F401

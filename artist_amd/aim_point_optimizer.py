@@ -22,7 +22,7 @@ from typing import Any
 
 import torch
 
-from . import _lib, distributed, training
+from . import _lib, distributed, optics, training
 from .flux import KLDivergenceLoss
 from .raytracing import HeliostatRayTracer
 
@@ -124,6 +124,12 @@ def _gpu_device(device) -> torch.device:
 class AimPointOptimizer:
     """``artist.optim.AimPointOptimizer``: see the module docstring; attributes as in the reference (:28-61).
 
+    ``attenuation`` (keyword only, an extension): a model of ``artist_amd.optics`` - ``("exponential", beta_per_km)``,
+    ``("polynomial", coefficients)`` or a callable.  ``prepare`` then computes every heliostat's extinction over its slant range to
+    the optimised target's centre once, and every epoch traces with it and with the group's ``active_reflectivities`` when the
+    group has them (the per-target bitmaps are then summed from scaled per-heliostat bitmaps,
+    ``HeliostatRayTracer.trace_rays_per_target``).  Without either, an epoch is what it was.
+
     ``blocking_active`` (True, as the reference always traces) may be cleared on an instance to see an epoch without
     blocking; ``prepare`` / ``trace_epoch`` / ``epoch_loss`` are the pieces ``optimize`` runs, for callers that step
     themselves."""
@@ -131,10 +137,12 @@ class AimPointOptimizer:
     def __init__(self, ddp_setup: dict, scenario, optimization_configuration: dict[str, Any], incident_ray_direction: torch.Tensor,
                  target_area_index: int, ground_truth: torch.Tensor, dni: float,
                  bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), epsilon: float = 1e-12,
-                 device: torch.device | None = None) -> None:
+                 device: torch.device | None = None, *, attenuation=None) -> None:
         _gpu_device(device)
         if ddp_setup["rank"] == 0:
             log.info("Create an aim points optimizer.")
+        #: atmospheric attenuation by slant range (an extension): None, or a model of ``artist_amd.optics``
+        self.attenuation = attenuation
         self.ddp_setup = ddp_setup
         self.scenario = scenario
         self.optimizer_dict = optimization_configuration["optimization"]
@@ -187,8 +195,12 @@ class AimPointOptimizer:
             limits = group.kinematics.actuators.non_optimizable_parameters
             scale = torch.minimum(initial - limits[:, ACTUATOR_MIN_MOTOR_POSITION],
                                   limits[:, ACTUATOR_MAX_MOTOR_POSITION] - initial).clamp(min=1.0)
+            extinction = None
+            if self.attenuation is not None:        # once: positions and the target's centre do not move with the motors
+                with torch.no_grad():
+                    extinction, _ = optics.heliostat_intensity_factors(group, tower, targets, self.attenuation)
             self.groups.append(dict(group=group, mask=mask, targets=targets, incident=directions, initial=initial, scale=scale,
-                                    parameter=torch.nn.Parameter(torch.zeros_like(initial)), offset=offset))
+                                    parameter=torch.nn.Parameter(torch.zeros_like(initial)), offset=offset, extinction=extinction))
             offset += n
         self.number_of_heliostats = offset
 
@@ -225,9 +237,16 @@ class AimPointOptimizer:
                                         world_size=ddp["heliostat_group_world_size"], rank=ddp["heliostat_group_rank"],
                                         batch_size=self.optimizer_dict["batch_size"], random_seed=ddp["heliostat_group_rank"],
                                         bitmap_resolution=self._resolution_cpu, dni=self.dni)
+            # per-heliostat optics (an extension): the extinction over each slant range and the group's reflectivities, when
+            # there are any - without them the call is the one it was
+            optics_arguments = {}
+            if g["extinction"] is not None:
+                optics_arguments["ray_extinction_factor"] = g["extinction"]
+            if getattr(group, "active_reflectivities", None) is not None:
+                optics_arguments["mirror_reflectivity"] = group.active_reflectivities
             per_target, intercept, on_target, blocking = tracer.trace_rays_per_target(
                 incident_ray_directions=g["incident"], active_heliostats_mask=g["mask"], target_area_indices=g["targets"],
-                device=device)
+                device=device, **optics_arguments)
             flux = per_target[self.target_area_index]
             total_flux = flux if total_flux is None else total_flux + flux
             rows = g["offset"] + tracer.get_sampler_indices().to(device)

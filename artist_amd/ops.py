@@ -460,10 +460,85 @@ class TraceRays(torch.autograd.Function):
         return (g_o, g_n) + (None,) * 14 + (g_pc, g_ps, g_pn, None, None, None, None) + (g_sc, g_ss, g_sn, None, None, None)
 
 
+_FACTOR_CHECKS = _memo.Memo("the host check of a per-heliostat intensity factor", capacity=8)
+
+
+def split_intensity_factors(extinction, reflectivity, n_heliostats: int, device, checked: "_memo.Memo" = _FACTOR_CHECKS):
+    """``(extinction for the kernel, reflectivity for the kernel, extinction [H] or None, reflectivity [H] or None)``.
+
+    A Python number, a 0-d tensor or a one-element tensor is a float for the kernel (what every call did before tensors were
+    accepted: same launches, same bits).  A tensor with more elements is one value per heliostat: the kernel then runs with
+    extinction 0 / reflectivity 1 for that factor and :func:`scale_heliostat_rows` applies it to the results.  Such a tensor is
+    ``[n_heliostats]``, floating point, on ``device``, finite, ``0 <= extinction <= 1``, ``reflectivity >= 0``: checked with one
+    fused reduction and one host read per tensor object and version (``checked``, artist_amd/_memo.py), not per call."""
+    out = []
+    for name, value, neutral in (("ray_extinction_factor", extinction, 0.0), ("mirror_reflectivity", reflectivity, 1.0)):
+        if not isinstance(value, torch.Tensor) or value.numel() <= 1:
+            out.append((float(value), None))
+            continue
+        if value.dim() != 1 or value.shape[0] != int(n_heliostats):
+            raise ValueError(f"{name} must be a float or one value per active heliostat, shape [{int(n_heliostats)}]; "
+                             f"got shape {tuple(value.shape)}")
+        if not value.dtype.is_floating_point:
+            raise ValueError(f"{name} must be a floating-point tensor, got {value.dtype}")
+        if value.device != torch.device(device):
+            raise ValueError(f"{name} must be on the device that traces, {torch.device(device)}; it is on {value.device}")
+
+        def check(name=name, value=value) -> bool:
+            lo, hi = torch.stack(torch.aminmax(value.detach().float())).tolist()      # (NaN propagates through both)
+            if not (math.isfinite(lo) and math.isfinite(hi)):
+                raise ValueError(f"{name} must be finite, got values in [{lo}, {hi}]")
+            if name == "ray_extinction_factor" and not (0.0 <= lo and hi <= 1.0):
+                raise ValueError(f"ray_extinction_factor must lie in [0, 1], got values in [{lo}, {hi}]")
+            if name == "mirror_reflectivity" and lo < 0.0:
+                raise ValueError(f"mirror_reflectivity must be >= 0, got values in [{lo}, {hi}]")
+            return True
+        checked.lookup(value, check, key=name)
+        out.append((neutral, value))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def scale_heliostat_rows(flux: torch.Tensor, factors: torch.Tensor, extinction, reflectivity):
+    """Per-heliostat intensity factors on the results of a trace that ran without them: bitmap row ``h`` times
+    ``w_h = (1 - extinction_h) * reflectivity_h`` in fp32 - ONE differentiable element-wise op on ``[H,Hh,W]`` (gradients reach
+    the surfaces through ``TraceRays.backward`` and a factor tensor that requires them) - and the intercept factor, which
+    counts rays with intensity > 0, set to 0 where ``w_h == 0``.  Either factor may be None (already in the kernel).
+
+    The result is not an untouched trace output: it has no ``bitmap_moments`` (the fused crop forms its own sums - the same
+    bits with or without them)."""
+    w = None if extinction is None else 1.0 - extinction.float()
+    if reflectivity is not None:
+        w = reflectivity.float() if w is None else w * reflectivity.float()
+    flux = flux * w.view(-1, 1, 1)
+    intercept = factors[0].masked_fill(w.detach() == 0, 0.0)
+    return flux, torch.cat((intercept.unsqueeze(0), factors[1:]))
+
+
 def trace_rays(origins, normals, incident, dist_u, dist_e, target_idx, centers, plane_normals, dims,
                ray_magnitude=1.0, extinction=0.0, reflectivity=0.935, resolution=(256, 256), per_target=False,
                cyl=None, blocking=None, points_per_facet=0, shading=None):
-    """Functional form.  Returns ``(flux, factors)`` with ``flux`` ``[H,Hh,W]`` (or ``[T+Tc,Hh,W]`` when
+    """Functional form; see :func:`_trace_rays` for the arguments.  ``extinction`` and ``reflectivity`` are each a float or a
+    tensor ``[H]``, one value per heliostat: a tensor is applied to the traced bitmaps
+    (:func:`scale_heliostat_rows`), and with ``per_target`` the scaled ``[H,Hh,W]`` bitmaps are then summed per target
+    (``art_per_target_sum``) - the fused per-target mode sums inside the kernel and cannot take them."""
+    extinction, reflectivity, ext_rows, refl_rows = split_intensity_factors(extinction, reflectivity, origins.shape[0],
+                                                                            origins.device)
+    if ext_rows is None and refl_rows is None:
+        return _trace_rays(origins, normals, incident, dist_u, dist_e, target_idx, centers, plane_normals, dims, ray_magnitude,
+                           extinction, reflectivity, resolution, per_target, cyl, blocking, points_per_facet, shading)
+    flux, factors, *flags = _trace_rays(origins, normals, incident, dist_u, dist_e, target_idx, centers, plane_normals, dims,
+                                        ray_magnitude, extinction, reflectivity, resolution, False, cyl, blocking,
+                                        points_per_facet, shading)
+    flux, factors = scale_heliostat_rows(flux, factors, ext_rows, refl_rows)
+    if per_target:
+        flux = per_target_sum(flux, target_idx, int(centers.shape[0]) + (0 if cyl is None else int(cyl[0].shape[0])))
+    return (flux, factors, *flags)
+
+
+def _trace_rays(origins, normals, incident, dist_u, dist_e, target_idx, centers, plane_normals, dims,
+                ray_magnitude=1.0, extinction=0.0, reflectivity=0.935, resolution=(256, 256), per_target=False,
+                cyl=None, blocking=None, points_per_facet=0, shading=None):
+    """Returns ``(flux, factors)`` with ``flux`` ``[H,Hh,W]`` (or ``[T+Tc,Hh,W]`` when
     ``per_target``) and ``factors`` ``[3,H]`` = intercept, on-target, blocking fractions.  ``cyl`` = the six
     ``TowerTargetAreasCylindrical`` tensors (centers, normals, axes, radii, heights, opening_angles) or None.
     ``blocking`` = None or a dict with ``corners [N,4,4]``, ``spans [N,2,4]``, ``normals [N,4]``, ``owner [H]`` and

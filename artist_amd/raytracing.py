@@ -118,6 +118,9 @@ class HeliostatRayTracer:
             number_of_active_heliostats=number_of_samples,
             random_seed=random_seed,
             rows=self.distortions_sampler.rank_indices if self.world_size > 1 else None,
+            # sigma of each heliostat's optical error (an extension; None in the reference's groups): the tensor itself on one
+            # rank, so that the sun's sample cache recognises it
+            optical_errors=getattr(self.heliostat_group, "active_optical_errors", None),
         )
         self.bitmap_resolution = bitmap_resolution
         self._resolution_host = (int(bitmap_resolution[0]), int(bitmap_resolution[1]))
@@ -160,6 +163,7 @@ class HeliostatRayTracer:
         # what a trace call learns from its arguments by a host read: once per tensor object and version (artist_amd/_memo.py),
         # so index tensors and masks are changed with tracked in-place ops, or replaced
         self._checked_targets = Memo("the host check of target_area_indices")
+        self._checked_factors = Memo("the host check of a per-heliostat intensity factor", capacity=4)
         self._owner = Memo("the rectangle index of each active heliostat (nonzero)")
         self._scatter_angle = Memo("the largest scatter angle of the distortions")
 
@@ -208,9 +212,15 @@ class HeliostatRayTracer:
 
         tower = self.scenario.solar_tower
         self._validate_targets(target_area_indices, tower)
+        # a float goes to the kernel as before; a tensor [H] is applied to the traced bitmaps (ops.scale_heliostat_rows)
+        ray_extinction_factor, mirror_reflectivity, extinction_rows, reflectivity_rows = ops.split_intensity_factors(
+            ray_extinction_factor, mirror_reflectivity, int(group.number_of_active_heliostats), points.device, self._checked_factors)
+        scaled = extinction_rows is not None or reflectivity_rows is not None
         idx, dist_u, dist_e = self._local_rows(device)
         if idx is not None:
             points, normals = points.index_select(0, idx), normals.index_select(0, idx)
+            extinction_rows = None if extinction_rows is None else extinction_rows.index_select(0, idx)
+            reflectivity_rows = None if reflectivity_rows is None else reflectivity_rows.index_select(0, idx)
             incident_ray_directions = incident_ray_directions.index_select(0, idx)
             target_area_indices = target_area_indices.index_select(0, idx)
 
@@ -225,11 +235,16 @@ class HeliostatRayTracer:
                        bool(self.blocking_active))
         flux, factors, flags = ops.TraceRays.apply(
             points, normals, incident_ray_directions, dist_u, dist_e, target_area_indices, *_planar_tables(tower, points.device),
-            float(self.ray_magnitude), float(ray_extinction_factor), float(mirror_reflectivity), width, height, bool(per_target),
+            float(self.ray_magnitude), float(ray_extinction_factor), float(mirror_reflectivity), width, height,
+            bool(per_target) and not scaled,
             _cylinder_tables(tower), *(rectangles or (None, None, None, None, -1.0, True)),
             self._points_per_facet(points), *shading)
         if self.blocking_active:
             self._filter_flags, self._filtered = flags, None       # (indices on demand: nonzero() waits for the device)
+        if scaled:
+            flux, factors = ops.scale_heliostat_rows(flux, factors, extinction_rows, reflectivity_rows)
+            if per_target:      # (the fused per-target mode sums inside the kernel: trace per heliostat, scale, then sum)
+                flux = ops.per_target_sum(flux, target_area_indices, sum(target_area_counts(tower)))
         return flux, factors[0], factors[1], factors[2]
 
     def trace_rays(self, incident_ray_directions: torch.Tensor, active_heliostats_mask: torch.Tensor,
@@ -238,7 +253,15 @@ class HeliostatRayTracer:
                    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """Heliostat ray tracing (:220-508).  Returns ``(flux [H,res_u,res_e], intercept_factor [H],
         on_target_factor [H], blocking_factor [H])`` for the heliostat samples owned by this rank.  With ``shading_active``
-        the blocking factor is the fraction of rays that are neither blocked nor shaded."""
+        the blocking factor is the fraction of rays that are neither blocked nor shaded.
+
+        ``ray_extinction_factor`` and ``mirror_reflectivity`` are, independently, a float for the whole field (the reference's
+        form; a 0-d or one-element tensor counts as one) or a tensor ``[H]``: one value per active heliostat in activation
+        order, field-wide, on the tracer's device - a rank takes its own rows, as it does for the other arguments.  A tensor
+        is not handed to the kernel (which then runs with extinction 0 / reflectivity 1 for that factor): bitmap row ``h`` is
+        multiplied by ``(1 - eps_h) * rho_h`` afterwards, one differentiable op, so a factor tensor that requires grad
+        receives its gradient; the intercept factor of a row with weight 0 is 0.  Such bitmaps are not untouched trace
+        outputs: ``ops.bitmap_moments`` has nothing for them and the fused crop forms its own sums (the same bits)."""
         return self._trace(incident_ray_directions, active_heliostats_mask, target_area_indices, ray_extinction_factor,
                            mirror_reflectivity, device, per_target=False)
 
@@ -313,7 +336,11 @@ class HeliostatRayTracer:
         """``trace_rays`` + ``get_bitmaps_per_target`` without materialising ``[H,res,res]``: every
         heliostat's rays are splatted straight into its target's bitmap (``[T,res_u,res_e]``, planar areas
         first, cylindrical second).  Extension of the reference API for field-scale flux prediction
-        (configs 3 and 5)."""
+        (configs 3 and 5).
+
+        With a tensor ``[H]`` for either intensity factor (see ``trace_rays``) the fused mode cannot be used - it sums
+        inside the kernel: the heliostats' bitmaps are traced, scaled and then summed (``art_per_target_sum``), so
+        ``[H,res_u,res_e]`` IS materialised; the result equals ``get_bitmaps_per_target(trace_rays(...))`` bit for bit."""
         return self._trace(incident_ray_directions, active_heliostats_mask, target_area_indices, ray_extinction_factor,
                            mirror_reflectivity, device, per_target=True)
 

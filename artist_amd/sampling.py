@@ -29,11 +29,23 @@ class DistortionsDataset(torch.utils.data.Dataset):
     """
 
     def __init__(self, light_source, number_of_points_per_heliostat: int, number_of_active_heliostats: int,
-                 random_seed: int = 7, rows=None) -> None:
+                 random_seed: int = 7, rows=None, optical_errors: torch.Tensor | None = None) -> None:
         self.rows = None if rows is None else [int(r) for r in rows]
         if self.rows is not None and len(self.rows) == number_of_active_heliostats and \
                 self.rows == list(range(number_of_active_heliostats)):
             self.rows = None
+        # ``optical_errors`` (an extension): sigma in rad of every active heliostat's optical error, ``[H]`` field-wide; the
+        # light source adds ``sigma_row * z`` to the rays of each row (``artist_amd.scene.Sun.get_distortions_rows``).  None
+        # (the default) passes nothing on: a light source that does not know the argument is called as before.
+        self._errors = {}
+        if optical_errors is not None:
+            if not isinstance(optical_errors, torch.Tensor) or tuple(optical_errors.shape) != (int(number_of_active_heliostats),):
+                raise ValueError(f"optical_errors must be a tensor with one sigma per active heliostat, shape "
+                                 f"[{int(number_of_active_heliostats)}]; got {tuple(getattr(optical_errors, 'shape', ()))}")
+            if self.rows is not None:
+                optical_errors = optical_errors.index_select(
+                    0, torch.tensor(self.rows, dtype=torch.long, device=optical_errors.device))
+            self._errors = dict(optical_errors=optical_errors)
         sliced = None
         if self.rows is not None:
             sliced = self._sample_rows(light_source, number_of_points_per_heliostat, number_of_active_heliostats, random_seed)
@@ -43,7 +55,7 @@ class DistortionsDataset(torch.utils.data.Dataset):
         self.distortions_u, self.distortions_e = light_source.get_distortions(
             number_of_points=number_of_points_per_heliostat,
             number_of_active_heliostats=number_of_active_heliostats,
-            random_seed=random_seed,
+            random_seed=random_seed, **self._errors,      # (errors with rows never get here: _sample_rows drew or raised)
         )
         if self.rows is not None:
             idx = torch.tensor(self.rows, dtype=torch.long, device=self.distortions_u.device)
@@ -59,9 +71,12 @@ class DistortionsDataset(torch.utils.data.Dataset):
             return both[..., 0], both[..., 1]
         if hasattr(light_source, "get_distortions_rows"):
             got = light_source.get_distortions_rows(self.rows, number_of_points=n_points,
-                                                    number_of_active_heliostats=n_heliostats, random_seed=seed)
+                                                    number_of_active_heliostats=n_heliostats, random_seed=seed, **self._errors)
             if got is not None:
                 return got
+        if self._errors:
+            raise ValueError("optical_errors need a light source that draws each heliostat's rows from a stream of their own "
+                             "(artist_amd.scene.Sun on the GPU)")
         dist = getattr(light_source, "distribution", None)
         n_rays = getattr(light_source, "number_of_rays", None)
         if not isinstance(dist, torch.distributions.MultivariateNormal) or n_rays is None or dist.loc.device.type != "cpu" \

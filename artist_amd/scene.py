@@ -34,6 +34,17 @@ BUIE_EXTENT = 43.6e-3                   # rad: where Buie's circumsolar profile 
 RADIAL_TABLE_INTERVALS = 1024           # K of the "buie" and "tabulated" tables (a pillbox is exact with K = 1)
 
 
+#: The stream of a heliostat's optical error is the sun's with the seed XOR this: the 64-bit golden-ratio
+#: constant, non-zero, so that the two Philox keys (seed, row) differ and a Gaussian sun is independent of its error.
+OPTICAL_ERROR_STREAM = 0x9E3779B97F4A7C15
+_NO_CPU_ERRORS = ("optical_errors are not supported with a light source on the CPU: its sample is the reference's one seeded "
+                  "MultivariateNormal stream, which has no second stream per heliostat; put the sun on the GPU")
+
+
+def _error_seed(random_seed: int) -> int:
+    return (int(random_seed) & 0xFFFFFFFFFFFFFFFF) ^ OPTICAL_ERROR_STREAM
+
+
 def buie_profile(circumsolar_ratio: float):
     """Buie, Monger and Dey (2003): radiance ``B(theta)``, ``theta`` in rad (numpy in, numpy out).  With theta in mrad,
     ``B = cos(0.326 theta) / cos(0.308 theta)`` on the disc (``theta <= 4.65``), ``exp(kappa) theta^gamma`` in the aureole
@@ -199,6 +210,7 @@ class Sun:
             self.distribution = RadialSunShape(mean, _radial_table(params).to(mean.device))
         self._law = Memo("the host copy of the sun's law")      # see _host_law
         self._cache = None          # (key, buffer, buffer version, table, table version) of the last "hip" draw
+        self._cache_errors = None   # the last "hip" draw with optical errors (see _hip_rows_with_errors)
         self._sampler = None
         self.sampler = sampler
 
@@ -212,7 +224,7 @@ class Sun:
             raise ValueError(f"Unknown distortion sampler {name!r}; expected one of {SAMPLERS}.")
         if name != self._sampler:
             self._sampler = name
-            self._cache = None
+            self._cache = self._cache_errors = None
 
     @property
     def quantile_table(self) -> torch.Tensor | None:
@@ -228,7 +240,7 @@ class Sun:
 
     def clear_distortion_cache(self) -> None:
         """Drop the kept ``"hip"`` sample (its memory is freed once no caller holds a view of it)."""
-        self._cache = None
+        self._cache = self._cache_errors = None
 
     @classmethod
     def from_hdf5(cls, config_file, light_source_name: str | None = None, device: torch.device | None = None,
@@ -239,19 +251,24 @@ class Sun:
         return cls(number_of_rays=t["number_of_rays"], distribution_parameters=t["distribution_parameters"], device=device,
                    sampler=sampler)
 
-    def get_distortions(self, number_of_points: int, number_of_active_heliostats: int, random_seed: int = 7):
+    def get_distortions(self, number_of_points: int, number_of_active_heliostats: int, random_seed: int = 7,
+                        optical_errors: torch.Tensor | None = None):
+        """All rows of the ``[H,R,P]`` distortion views; ``optical_errors``: see :meth:`get_distortions_rows`."""
         if self._sampler == "hip":
-            return self._hip_rows(range(number_of_active_heliostats), number_of_points, random_seed)
+            return self._hip_rows(range(number_of_active_heliostats), number_of_points, random_seed, optical_errors)
         loc = self.distribution.loc
         if loc.device.type == "cpu":
+            if optical_errors is not None:
+                raise ValueError(_NO_CPU_ERRORS)
             torch.manual_seed(random_seed)
             sample = self.distribution.sample((number_of_active_heliostats, self.number_of_rays, number_of_points))
             distortions_u, distortions_e = sample.permute(3, 0, 1, 2)
             return distortions_u, distortions_e
         return self.get_distortions_rows(range(number_of_active_heliostats), number_of_points, number_of_active_heliostats,
-                                         random_seed)
+                                         random_seed, optical_errors)
 
-    def get_distortions_rows(self, rows, number_of_points: int, number_of_active_heliostats: int, random_seed: int = 7):
+    def get_distortions_rows(self, rows, number_of_points: int, number_of_active_heliostats: int, random_seed: int = 7,
+                             optical_errors: torch.Tensor | None = None):
         """Rows ``rows`` of the ``[H,R,P]`` distortion views when the light source lives on the GPU (None on the CPU: the
         caller then slices the reference's one seeded stream, ``artist_amd.sampling.DistortionsDataset``).
 
@@ -263,34 +280,67 @@ class Sun:
 
         ``sampler == "torch"``: a seeded ``torch.randn`` per row (``torch.rand`` and the table rule for a radial sun);
         ``"hip"``: ``art_sample_distortions`` / ``art_sample_radial_distortions`` (Philox4x32-10 keyed by (seed, row),
-        DESIGN.md 4.5), cached per sun (class docstring), and no CPU fallback."""
+        DESIGN.md 4.5), cached per sun (class docstring), and no CPU fallback.
+
+        ``optical_errors`` (an extension): sigma in rad of each requested row's optical error - the mirror's
+        specular and slope roughness, which a sun shape that is the sun alone leaves out - a tensor ``[len(rows)]``, ``>= 0``,
+        on the sun's device.  The distortion of ray ``(row, r, p)`` is then the sun's draw plus ``sigma_row * z``, ``z`` a
+        standard normal pair from a second stream per (seed, row) that is independent of the sun's: the seed XOR
+        ``OPTICAL_ERROR_STREAM``.  With any sun shape; a row with sigma 0 is the plain draw bit for bit; None is the plain
+        draw.  Not with a light source on the CPU (``ValueError``): its rows come from the reference's one stream."""
         if self._sampler == "hip":
-            return self._hip_rows(rows, number_of_points, random_seed)
+            return self._hip_rows(rows, number_of_points, random_seed, optical_errors)
         dist = self.distribution
         loc = dist.loc
         if loc.device.type == "cpu":
+            if optical_errors is not None:
+                raise ValueError(_NO_CPU_ERRORS)
             return None
         radial = isinstance(dist, RadialSunShape)
-        draw = torch.rand if radial else torch.randn
         rows = [int(r) for r in rows]
-        out = torch.empty((len(rows), self.number_of_rays, number_of_points, 2), dtype=loc.dtype, device=loc.device)
-        gen = torch.Generator(device=loc.device)
-        for k, row in enumerate(rows):
-            gen.manual_seed((int(random_seed) * 1000003 + row) & 0x7FFFFFFFFFFFFFFF)
-            draw(out[k].shape, generator=gen, dtype=loc.dtype, device=loc.device, out=out[k])
+        if optical_errors is not None:
+            self._check_optical_errors(optical_errors, len(rows))
+
+        def seeded(draw, seed) -> torch.Tensor:
+            out = torch.empty((len(rows), self.number_of_rays, number_of_points, 2), dtype=loc.dtype, device=loc.device)
+            gen = torch.Generator(device=loc.device)
+            for k, row in enumerate(rows):
+                gen.manual_seed((seed * 1000003 + row) & 0x7FFFFFFFFFFFFFFF)
+                draw(out[k].shape, generator=gen, dtype=loc.dtype, device=loc.device, out=out[k])
+            return out
+
+        out = seeded(torch.rand if radial else torch.randn, int(random_seed))
         if radial:
-            distortions_u, distortions_e = dist.transform_(out).permute(3, 0, 1, 2)
-            return distortions_u, distortions_e
-        tril = dist.scale_tril
-        if float(tril[1, 0]) != 0.0:
-            out[..., 1] = tril[1, 0] * out[..., 0] + tril[1, 1] * out[..., 1]
+            out = dist.transform_(out)
         else:
-            out[..., 1] *= tril[1, 1]
-        out[..., 0] *= tril[0, 0]
-        if float(loc.abs().max()) != 0.0:
-            out += loc
+            tril = dist.scale_tril
+            if float(tril[1, 0]) != 0.0:
+                out[..., 1] = tril[1, 0] * out[..., 0] + tril[1, 1] * out[..., 1]
+            else:
+                out[..., 1] *= tril[1, 1]
+            out[..., 0] *= tril[0, 0]
+            if float(loc.abs().max()) != 0.0:
+                out += loc
+        if optical_errors is not None:
+            z = seeded(torch.randn, _error_seed(random_seed))
+            out = torch.addcmul(out, z, optical_errors.detach().to(loc.dtype).view(-1, 1, 1, 1))
         distortions_u, distortions_e = out.permute(3, 0, 1, 2)
         return distortions_u, distortions_e
+
+    def _check_optical_errors(self, optical_errors, n_rows: int) -> None:
+        """Shape, dtype, device and values of ``optical_errors`` (one reduction and one host read, before a draw only)."""
+        device = self.distribution.loc.device
+        if not isinstance(optical_errors, torch.Tensor) or tuple(optical_errors.shape) != (n_rows,):
+            raise ValueError(f"optical_errors must be a tensor with one sigma per requested row, shape [{n_rows}]; "
+                             f"got {tuple(getattr(optical_errors, 'shape', ()))}")
+        if not optical_errors.dtype.is_floating_point:
+            raise ValueError(f"optical_errors must be a floating-point tensor, got {optical_errors.dtype}")
+        if optical_errors.device != device:
+            raise ValueError(f"optical_errors must be on the sun's device, {device}; it is on {optical_errors.device}")
+        if n_rows:
+            lo, hi = torch.stack(torch.aminmax(optical_errors.detach().float())).tolist()      # (NaN propagates through both)
+            if not (math.isfinite(lo) and math.isfinite(hi)) or lo < 0.0:
+                raise ValueError(f"optical_errors must be finite and >= 0, got values in [{lo}, {hi}]")
 
     def _host_law(self):
         """``(loc, scale_tril)`` of the current distribution as host floats (``(loc, None)`` for a radial sun, whose table stays
@@ -314,13 +364,17 @@ class Sun:
         #  around the same tensors has the same law)
         return self._law.lookup((loc, tril), read, key=radial)
 
-    def _hip_rows(self, rows, number_of_points: int, random_seed: int):
+    def _hip_rows(self, rows, number_of_points: int, random_seed: int, optical_errors=None):
         from . import _lib, ops
         loc = self.distribution.loc
         if loc.device.type != "cuda":
+            if optical_errors is not None and loc.device.type == "cpu":
+                raise ValueError(_NO_CPU_ERRORS)
             raise _lib.ArtistHipError(f"Sun(sampler='hip') draws on the GPU only (the light source is on {loc.device}); "
                                       "there is no CPU fallback")
         rows = tuple(int(r) for r in rows)
+        if optical_errors is not None:
+            return self._hip_rows_with_errors(rows, number_of_points, random_seed, optical_errors)
         law = self._host_law()
         table = self.quantile_table     # a radial sun's law: the same tensor, unwritten since the draw (None: a normal sun)
         key = (int(random_seed), rows, int(self.number_of_rays), int(number_of_points), loc.device, law)
@@ -337,6 +391,31 @@ class Sun:
             else:
                 buf = ops.sample_radial_distortions(rows, key[2], key[3], key[0], law[0], table, loc.device)
             self._cache = (key, buf, buf._version, table, None if table is None else table._version)
+        distortions_u, distortions_e = buf.permute(3, 0, 1, 2)
+        return distortions_u, distortions_e
+
+    def _hip_rows_with_errors(self, rows: tuple, number_of_points: int, random_seed: int, optical_errors):
+        """The plain draw (the cached base sample: shared, read only) plus ``sigma_row * z``, ``z`` from one more
+        ``art_sample_distortions`` launch with ``loc = 0``, ``scale_tril = I`` and the seed XOR ``OPTICAL_ERROR_STREAM``, combined
+        by one ``addcmul`` into a buffer of its own.  That buffer is kept like the base sample, its key the base sample's
+        buffer and version and the errors tensor's identity and version: the same tensor, unwritten, draws nothing."""
+        from . import _lib, ops
+        base_u, _ = self._hip_rows(rows, number_of_points, random_seed)
+        base = self._cache[1]
+        kept = self._cache_errors
+        if kept is not None and kept[0] is base and kept[1] == base._version and kept[2] is optical_errors and \
+                kept[3] == optical_errors._version and kept[4]._version == kept[5]:
+            buf = kept[4]
+        else:
+            if _lib.capturing():
+                raise _lib.first_use_under_capture("the sun's distortion sample")
+            self._cache_errors = None
+            self._check_optical_errors(optical_errors, len(rows))
+            z = ops.sample_distortions(rows, int(self.number_of_rays), int(number_of_points), _error_seed(random_seed),
+                                       (0.0, 0.0), ((1.0, 0.0), (0.0, 1.0)), base.device)
+            # (into z's own memory, element by element: the base sample is only read, and no third buffer of 8 B per ray exists)
+            buf = torch.addcmul(base, z, optical_errors.detach().float().view(-1, 1, 1, 1), out=z)
+            self._cache_errors = (base, base._version, optical_errors, optical_errors._version, buf, buf._version)
         distortions_u, distortions_e = buf.permute(3, 0, 1, 2)
         return distortions_u, distortions_e
 
@@ -471,6 +550,11 @@ class HeliostatGroup:
         self.facet_translations = facet_translations
         self.nurbs_control_points = nurbs_control_points
         self.nurbs_degrees = nurbs_degrees
+        #: per-heliostat optics (an extension), each None or a tensor ``[number_of_heliostats]``: the mirrors'
+        #: reflectivity, and sigma in rad of their optical error.  ``activate_heliostats`` expands them to ``active_reflectivities``
+        #: / ``active_optical_errors``; nothing reads them while they are None
+        self.reflectivities = self.optical_errors = None
+        self.active_reflectivities = self.active_optical_errors = None
         self.number_of_active_heliostats = 0
         self.active_heliostats_mask = torch.zeros(self.number_of_heliostats, dtype=torch.int32, device=device)
         self.active_surface_points = torch.empty_like(surface_points)
@@ -491,6 +575,8 @@ class HeliostatGroup:
         self.active_facet_translations = rep(self.facet_translations)
         self.active_nurbs_control_points = rep(self.nurbs_control_points)
         self.active_positions = rep(self.positions)
+        self.active_reflectivities = None if self.reflectivities is None else rep(self.reflectivities)
+        self.active_optical_errors = None if self.optical_errors is None else rep(self.optical_errors)
         kin = self.kinematics
         if kin is not None:                                              # heliostat_group.py:273-315
             kin.number_of_active_heliostats = self.number_of_active_heliostats
