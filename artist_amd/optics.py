@@ -10,12 +10,77 @@ An attenuation ``model`` is one of
 * ``("polynomial", coefficients)``: the LOSS fraction is ``sum_k c_k d^k`` (``d`` in km, ``c_0`` first), clamped to [0, 1] - the
   form of the DELSOL / Leary-Hankins fits.  No coefficients are shipped: take them from the source you trust;
 * a callable ``slant range in metres [H] -> transmittance [H]``.
+
+Mirror slope errors: :func:`tilt_normals` tilts surface normals by slope pairs before alignment,
+:func:`slope_sample` draws the standard-normal pairs of a group's heliostats, :func:`expand_over_samples` repeats per-heliostat
+rows over their activations with a fixed-order backward.
 """
 from __future__ import annotations
 
 import torch
 
-__all__ = ["slant_ranges", "atmospheric_transmittance", "heliostat_intensity_factors"]
+__all__ = ["slant_ranges", "atmospheric_transmittance", "heliostat_intensity_factors", "tilt_normals", "slope_sample",
+           "expand_over_samples", "SLOPE_ERROR_STREAM"]
+
+#: The stream of a mirror's slope-error sample is the sampler's with the seed XOR this (DESIGN.md 4.15): the 64-bit constant of
+#: the splitmix64 finaliser, non-zero and different from ``artist_amd.scene.OPTICAL_ERROR_STREAM``, so that the Philox keys
+#: (seed, row) of the sun, of the optical error and of the slope error all differ.
+SLOPE_ERROR_STREAM = 0xBF58476D1CE4E5B9
+_NO_CPU_SLOPES = ("slope errors are not drawn on the CPU: their sample comes from the HIP sampler's Philox streams, which have no "
+                  "CPU fallback; put the group on the GPU (or hand the group a sample of your own, HeliostatGroup.slope_sample)")
+
+
+def tilt_normals(normals: torch.Tensor, slopes: torch.Tensor) -> torch.Tensor:
+    """Surface normals ``[..., 4]`` in the heliostat's canonical frame (before alignment), each tilted by its slope pair
+    ``slopes [..., 2]``: with ``x = (1, 0, 0)``, ``t1 = normalize(x - (x.n) n)``, ``t2 = n x t1`` and
+    ``n' = normalize(n + a t1 + b t2)`` on the xyz part; w passes through.  ``(a, b)`` are slopes - the tangents of the tilt
+    angles about ``-t2`` and ``t1`` - the quantity deflectometry reports; any tensor will do, a measured residual map or
+    ``sigma * zeta`` with :func:`slope_sample`.  Torch ops, differentiable in both arguments, on whichever device they live;
+    zero slopes give ``normalize(n)`` bit for bit.  A normal along x has no ``t1`` and comes back as ``normalize(n)``."""
+    if normals.shape[-1] != 4 or slopes.shape[-1] != 2 or normals.shape[:-1] != slopes.shape[:-1]:
+        raise ValueError(f"normals must be [...,4] and slopes [...,2] with the same leading shape, got {tuple(normals.shape)} and "
+                         f"{tuple(slopes.shape)}")
+    normalize = torch.nn.functional.normalize
+    n = normals[..., :3]
+    x = torch.zeros_like(n)
+    x[..., 0] = 1.0
+    t1 = normalize(x - n[..., :1] * n, dim=-1)
+    t2 = torch.linalg.cross(n, t1, dim=-1)
+    tilted = normalize(n + slopes[..., :1] * t1 + slopes[..., 1:] * t2, dim=-1)
+    return torch.cat((tilted, normals[..., 3:]), dim=-1)
+
+
+def slope_sample(rows, number_of_points: int, seed: int, device) -> torch.Tensor:
+    """The standard-normal slope pairs ``zeta [len(rows), P, 2]`` of heliostats ``rows`` - their indices IN THE GROUP, not
+    active rows: a mirror keeps its roughness across samples, sun positions and ranks, so every activation of a heliostat shares
+    its realisation, and a rank's rows are the rows of the full draw.  One ``art_sample_distortions`` launch with one ray per
+    point, ``loc = 0``, ``scale_tril = I`` and the seed XOR ``SLOPE_ERROR_STREAM``.  On the GPU only (``ValueError`` otherwise)."""
+    from . import ops
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(_NO_CPU_SLOPES)
+    key = (int(seed) & 0xFFFFFFFFFFFFFFFF) ^ SLOPE_ERROR_STREAM
+    rows = [int(r) for r in rows]
+    return ops.sample_distortions(rows, 1, int(number_of_points), key, (0.0, 0.0), ((1.0, 0.0), (0.0, 1.0)), device).reshape(
+        len(rows), int(number_of_points), 2)
+
+
+def expand_over_samples(tensor: torch.Tensor, counts, rows: torch.Tensor | None = None) -> torch.Tensor:
+    """Row ``i`` of ``tensor [N, ...]`` ``counts[i]`` times, rows in order: the values of ``repeat_interleave(counts)``, whose
+    backward is an ``index_add`` with float atomics on the device.  Here the gradient of a row that is repeated is summed in a
+    fixed order: with one count for all rows that have any (the usual activation) the rows are taken once - ``rows``, their
+    indices on the tensor's device, or all of them for None - and expanded over the sample axis with a view, backwards
+    ``[rows, samples, ...].sum(1)``, as the kinematics reconstructor expands its deviations; with mixed counts, a
+    concatenation of per-row expansions."""
+    counts = [int(c) for c in counts]
+    taken = [i for i, c in enumerate(counts) if c]
+    shape = tuple(tensor.shape[1:])
+    if len({counts[i] for i in taken}) <= 1:
+        samples = counts[taken[0]] if taken else 0
+        if len(taken) != len(counts):
+            tensor = tensor.index_select(0, torch.tensor(taken, dtype=torch.long, device=tensor.device) if rows is None else rows)
+        return tensor.reshape(len(taken), 1, *shape).expand(len(taken), samples, *shape).reshape(len(taken) * samples, *shape)
+    return torch.cat([tensor[i:i + 1].expand(counts[i], *shape) for i in taken])
 
 
 def slant_ranges(active_positions: torch.Tensor, target_centres: torch.Tensor) -> torch.Tensor:

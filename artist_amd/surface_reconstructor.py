@@ -30,6 +30,10 @@ translations learn beside or instead of the control points.  Their active rows a
 takes the staged route (``art_nurbs_fwd`` without canting, ``art_cant_facets_fwd``; backwards ``art_cant_facets_bwd`` and, if
 the control points learn, ``art_nurbs_bwd``) - still once per heliostat and epoch, with the same fixed-order sum over the
 samples - and the gradient of the homogeneous w components is set to zero before the step.
+
+Slope errors: a group with ``slope_errors`` has every evaluated normal tilted by ``sigma_h * zeta`` (torch ops,
+``artist_amd.optics.tilt_normals``) once per heliostat and epoch, between the evaluation and the expansion over the samples;
+with ``"slope_errors"`` among the parameters sigma learns, its gradient arriving through the trace's gradient of the normals.
 """
 from __future__ import annotations
 
@@ -51,7 +55,7 @@ from .training import reduce_loss_per_sample
 log = logging.getLogger(__name__)
 
 __all__ = ["SurfaceReconstructor", "CalibrationSamples", "GroupState", "EpochLoss", "flux_integral_constraint", "HISTORY_KEYS",
-           "PARAMETER_NAMES", "LEARNING_RATE_KEYS", "canonical_parameters", "learning_rates", "tensors_held_by", "LearnsParameters"]
+           "PARAMETER_NAMES", "GEOMETRY_PARAMETER_NAMES", "LEARNING_RATE_KEYS", "canonical_parameters", "learning_rates", "tensors_held_by", "LearnsParameters"]
 
 #: the per-epoch lists of a group's history, in the order the epoch's scalars are stacked; ``"test_loss"`` comes on top
 HISTORY_KEYS = ("total_loss", "flux_loss", "smoothness_regularizer", "ideal_regularizer", "flux_integral",
@@ -59,14 +63,19 @@ HISTORY_KEYS = ("total_loss", "flux_loss", "smoothness_regularizer", "ideal_regu
 
 #: what a reconstruction can learn, in the canonical order: the order of the optimiser's parameter groups, of the reduces in
 #: nested mode and of the broadcasts after the run.  The names are the group's attributes.
-PARAMETER_NAMES = ("nurbs_control_points", "canting", "facet_translations")
+PARAMETER_NAMES = ("nurbs_control_points", "canting", "facet_translations", "slope_errors")
+
+#: the names whose rates :func:`learning_rates` reports when it is asked for none in particular: the tensors that shape the
+#: surface.  ``"slope_errors"`` (sigma per heliostat) has a rate when it is named.
+GEOMETRY_PARAMETER_NAMES = PARAMETER_NAMES[:3]
 
 _mean_over_samples = partial(torch.mean, dim=-1)
 
 
 #: the configuration key of every name's initial learning rate; the first is required and the default of the others
 LEARNING_RATE_KEYS = {"nurbs_control_points": "initial_learning_rate", "canting": "initial_learning_rate_canting",
-                      "facet_translations": "initial_learning_rate_facet_translations"}
+                      "facet_translations": "initial_learning_rate_facet_translations",
+                      "slope_errors": "initial_learning_rate_slope_errors"}
 
 
 def canonical_parameters(parameters, names=PARAMETER_NAMES) -> tuple:
@@ -83,12 +92,15 @@ def canonical_parameters(parameters, names=PARAMETER_NAMES) -> tuple:
 
 
 def learning_rates(optimizer_dict: dict, parameters=None, keys=LEARNING_RATE_KEYS) -> dict:
-    """The initial learning rate of every name in ``parameters`` (all of ``keys`` by default), in the canonical order, from
+    """The initial learning rate of every name in ``parameters`` (by default all of ``keys``; of the surface reconstructor's
+    own keys the three ``GEOMETRY_PARAMETER_NAMES``), in the canonical order, from
     the configuration's ``"optimization"`` table.  ``keys`` maps a reconstructor's parameter names, in their canonical order,
     to their configuration keys; the first key is required, the others are optional and default to it.  For the surface
     reconstructor (the default): ``"initial_learning_rate"`` for the control points, ``"initial_learning_rate_canting"`` and
-    ``"initial_learning_rate_facet_translations"`` for the two rigid tensors."""
+    ``"initial_learning_rate_facet_translations"`` for the two rigid tensors, ``"initial_learning_rate_slope_errors"`` for sigma."""
     names = tuple(keys)
+    if parameters is None and keys is LEARNING_RATE_KEYS:
+        parameters = GEOMETRY_PARAMETER_NAMES
     default = float(optimizer_dict[keys[names[0]]])
     return {name: float(optimizer_dict.get(keys[name], default))
             for name in canonical_parameters(names if parameters is None else parameters, names)}
@@ -189,6 +201,8 @@ class GroupState:
     # require grad before ``prepare`` marked them
     learnables: dict = field(default_factory=dict)
     marked: list = field(default_factory=list)
+    # a group with slope errors: zeta of the heliostats that have samples, [active, F, M, 2] (a constant of the run)
+    slope_sample: torch.Tensor | None = None
 
 
 def tensors_held_by(*holders, depth: int = 3) -> list:
@@ -275,7 +289,12 @@ class SurfaceReconstructor(LearnsParameters):
     components of both rigid tensors are homogeneous zeros and no parameters: their gradient is set to zero before the step
     (the alignment's adjoint leaves one on a translation's w), so they keep their bits.  Regularisers, constraint, histories,
     validation and the stop logic are the same for every choice; without the control points the two regulariser terms are
-    constants of the run.  After the run the rigid tensors that ``prepare`` marked no longer require grad."""
+    constants of the run.  After the run the rigid tensors that ``prepare`` marked no longer require grad.
+
+    ``"slope_errors"`` ``[N]`` is the fourth name: the group's sigma of the mirrors' slope error, which must be
+    set before :meth:`prepare` (``ValueError`` otherwise), at ``optimization["initial_learning_rate_slope_errors"]``.  Alone or
+    beside the others; the evaluation keeps the route the other names choose.  A sigma that learns is not checked for its sign
+    and is left as its magnitude, detached, on ``group.slope_errors``."""
 
     def __init__(self, ddp_setup: dict, scenario, data: dict, optimization_configuration: dict[str, Any],
                  dni: float | None = None, number_of_surface_points: torch.Tensor = torch.tensor([50, 50]),
@@ -312,8 +331,11 @@ class SurfaceReconstructor(LearnsParameters):
         ``self.parameters`` (``requires_grad_()`` on those, and on no other), the configured scheduler, early stopping and a
         zero multiplier.  None for a group without samples."""
         from .optim import Adam
-        device = _gpu_device(device)
         group = self.scenario.heliostat_field.heliostat_groups[heliostat_group_index]
+        if "slope_errors" in self.parameters and getattr(group, "slope_errors", None) is None:
+            raise ValueError(f"parameters={self.parameters!r}: heliostat group {heliostat_group_index} has no slope_errors to start "
+                             "from; set group.slope_errors to a tensor with one sigma per heliostat before the reconstruction")
+        device = _gpu_device(device)
         flux_measured, focal_spots, incident, motor_positions, mask, targets = self.data["data_parser"].parse_data_for_reconstruction(
             heliostat_data_mapping=self.data["heliostat_data_mapping"], heliostat_group=group, scenario=self.scenario,
             bitmap_resolution=self.bitmap_resolution, device=device)
@@ -345,6 +367,10 @@ class SurfaceReconstructor(LearnsParameters):
                            facet_translations=group.facet_translations.detach().index_select(0, active_rows),
                            optimizer=optimizer, scheduler=scheduler, early_stopper=stopper, multiplier=torch.zeros((), device=device),
                            learnables=learnables, marked=marked)
+        if getattr(group, "slope_errors", None) is not None:
+            group.checked_slope_errors()        # (the marked leaf: shape, dtype and device; a constant sigma: its values too)
+            facets = int(group.number_of_facets_per_heliostat)
+            state.slope_sample = group.slope_sample.index_select(0, active_rows).reshape(active, facets, -1, 2)
         _, heliostat_rows = self._rank_rows(state, "train", device)
         state.multiplier = torch.zeros(active if heliostat_rows is None else int(heliostat_rows.numel()), device=device)
         return state
@@ -390,6 +416,11 @@ class SurfaceReconstructor(LearnsParameters):
             else state.facet_translations
         points, normals = NURBSSurfaces(group.nurbs_degrees, nets, device=device).calculate_surface_points_and_normals(
             state.evaluation_points, canting, translations)
+        if state.slope_sample is not None:
+            # slope errors: tilted here, once per distinct heliostat and before the samples' expansion - the gradient lands on
+            # the group's own sigma, summed over the samples in the same fixed order - and not again in the alignment
+            normals = group.tilted_normals(normals, group.slope_errors.index_select(0, state.active_rows).reshape(-1, 1),
+                                           state.slope_sample)
         active, per_heliostat = points.shape[0], points.shape[1] * points.shape[2]
         repeat = lambda t: t.reshape(active, 1, per_heliostat, 4).expand(-1, samples, -1, -1).reshape(  # noqa: E731
             active * samples, per_heliostat, 4)              # backward: .sum(1) over the samples, a fixed order
@@ -408,7 +439,10 @@ class SurfaceReconstructor(LearnsParameters):
                 orientations = ideal_orientations(group.active_positions, aim_points, incident)
                 if state.static:            # (one of its constants comes from a host list: a copy that cannot be captured)
                     state.orientations[kind] = orientations
-        group._align(orientations)
+        if state.slope_sample is not None:
+            group._align(orientations, tilt=False)
+        else:
+            group._align(orientations)
 
         tracer = state.tracers.get(kind)
         if tracer is None:
@@ -560,12 +594,21 @@ class SurfaceReconstructor(LearnsParameters):
         with torch.no_grad():
             parameter.grad[..., 3] = 0
 
+    def _synchronize_gradients(self, parameter: torch.Tensor) -> None:
+        """The nested average alone, for ``slope_errors`` ``[N]``: every component is a parameter."""
+        ddp = self.ddp_setup
+        if parameter.grad is not None and ddp["is_nested"]:
+            distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
+            parameter.grad /= ddp["heliostat_group_world_size"]
+
     def _synchronize_and_lock_learnables(self, state: GroupState, device: torch.device | None = None) -> None:
         """Before the step: one reduce per learnable tensor in the canonical order (the same on every rank), the edge lock on
         the control points, the w rule on the rigid tensors."""
         for name, tensor in state.learnables.items():
             if name == "nurbs_control_points":
                 self._synchronize_and_lock_gradients(tensor, device)
+            elif name == "slope_errors":
+                self._synchronize_gradients(tensor)
             else:
                 self._synchronize_and_zero_w_gradients(tensor, device)
 
@@ -657,6 +700,9 @@ class SurfaceReconstructor(LearnsParameters):
                     self.close_epoch_graph(state)
                 for tensor in state.marked:             # the rigid tensors are constants again for whoever evaluates next
                     tensor.requires_grad_(False)
+                if "slope_errors" in state.learnables:  # zeta is symmetric: a learnt sigma is reported as its magnitude
+                    with torch.no_grad():
+                        state.learnables["slope_errors"].abs_()
             log.info(f"Rank: {rank}, Surfaces reconstructed.")
 
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history)
