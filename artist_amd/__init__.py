@@ -8,6 +8,8 @@ backward, behind ARTIST's own call surface:
     artist_amd.NURBSSurfaces        <-> artist.nurbs.NURBSSurfaces
     artist_amd.crop_flux_distributions_around_center, get_center_of_mass, PixelLoss, KLDivergenceLoss, FocalSpotLoss
                                     <-> artist.flux.bitmap / artist.optim.loss (the per-epoch flux epilogue)
+    artist_amd.JensenShannonLoss, ShapePixelLoss, TotalVariationLoss, CosineFluxLoss
+                                    (no counterpart) flux losses that do not depend on the gain of either bitmap
     artist_amd.RigidBody            <-> artist.field.kinematics_rigid_body.RigidBody (ideal + linear actuators)
     artist_amd.Scenario             <-> artist.scenario.scenario.Scenario (load_scenario_from_hdf5, index_mapping)
     artist_amd.optim.Adam           <-> torch.optim.Adam as the reconstructors use it (the epoch's optimiser step)
@@ -28,9 +30,9 @@ All arithmetic runs in hand-written HIP kernels (``artist_amd/csrc``) reached th
 """
 from ._lib import ArtistHipError, build, lib  # noqa: F401
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nurbs_control_points  # noqa: F401
-from .flux import (FocalSpotLoss, KLDivergenceLoss, PixelLoss, bitmap_coordinates_to_target_coordinates,  # noqa: F401
-                   crop_and_kl_loss, crop_and_pixel_loss, crop_flux_distributions_around_center, get_center_of_mass,
-                   trapezoid_distribution)
+from .flux import (CosineFluxLoss, FocalSpotLoss, JensenShannonLoss, KLDivergenceLoss, PixelLoss, ShapePixelLoss,  # noqa: F401
+                   TotalVariationLoss, bitmap_coordinates_to_target_coordinates, crop_and_kl_loss, crop_and_pixel_loss,
+                   crop_flux_distributions_around_center, get_center_of_mass, trapezoid_distribution)
 from .kinematics import Actuators, RigidBody  # noqa: F401
 from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, perform_canting, trace_rays  # noqa: F401
 from . import optics, optim, training  # noqa: F401

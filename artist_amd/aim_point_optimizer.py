@@ -23,7 +23,7 @@ from typing import Any
 import torch
 
 from . import _lib, distributed, optics, training
-from .flux import KLDivergenceLoss
+from .flux import JensenShannonLoss, KLDivergenceLoss
 from .raytracing import HeliostatRayTracer
 
 log = logging.getLogger(__name__)
@@ -107,7 +107,8 @@ def aim_point_objective(flux_loss: torch.Tensor, total_flux: torch.Tensor, inter
 
 
 def _require_kl(loss_definition) -> None:
-    if not isinstance(loss_definition, KLDivergenceLoss):
+    # (... or its bounded relative, the Jensen-Shannon divergence: the same kind of loss on the same normalised bitmaps)
+    if not isinstance(loss_definition, (KLDivergenceLoss, JensenShannonLoss)):
         raise TypeError("AimPointOptimizer defines its total loss (flux loss + flux-integral, intercept and local-flux "
                         f"constraints) for artist_amd.KLDivergenceLoss only, got {type(loss_definition).__name__}: with any "
                         "other loss definition there is no loss to differentiate")

@@ -6,7 +6,8 @@
 //          sums the few output pixels that sampled it): deterministic, no atomics - torch's grid_sample backward
 //          scatters with atomics.
 //   loss   PixelLoss / KLDivergenceLoss (artist/optim/loss.py:251-410) with the reduction over the two bitmap
-//          dimensions, forward and backward, one workgroup per sample.
+//          dimensions, forward and backward, one workgroup per sample; and the four gain-free kinds of art_flux_loss (Jensen-Shannon,
+//          shape pixel loss, total variation, cosine), which the reference does not have.
 //
 // All of it is HBM-bound elementwise / reduction work on [B,Hh,W] fp32: one read and one write of the bitmaps.
 #include <hip/hip_runtime.h>
@@ -457,6 +458,109 @@ __global__ __launch_bounds__(kReduceBlock) void flux_loss_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The gain-free kinds of art_flux_loss (include/artist_hip.h): 2 Jensen-Shannon, 3 shape pixel loss, 4 total variation on the
+// L1-normalised bitmaps p^ = p / dp, g^ = g / dg (norms and clamps as KlNorms forms them), 5 one minus the cosine similarity.
+// Kernels of their own, one per kind: flux_loss_kernel and its registers stay what they were.  Same shape as kind 1 - one
+// workgroup per bitmap, fp64 per-thread sums in for_each_pair's order, the block tree, no atomics: a bitmap's bits depend on
+// neither the batch nor the run.  The sums are over pixels that are formed again in the gradient pass (nothing is kept).
+// ---------------------------------------------------------------------------------------------------
+// One pixel of kinds 2 to 4: its share of the loss sum (before the kind's factor, see unit_l1_loss_factor) and a = dL/dp^_k.
+template <int KIND>
+__device__ __forceinline__ double unit_l1_pixel(float ph, float gh, float pixels, float& a)
+{
+    constexpr float eps = KlNorms::eps;
+    if constexpr (KIND == 2) {
+        // 1/2 sum u (log u - log w) + 1/2 sum v (log v - log w), u = g^ + eps, v = p^ + eps, w = (p^ + g^) / 2 + eps.  w moves
+        // by half of p^, and u + v = 2 w: what is left of the derivative is (log v - log w) / 2.
+        const float u = gh + eps, v = ph + eps;
+        const float lw = logf(0.5f * (ph + gh) + eps);
+        const float du = logf(u) - lw, dv = logf(v) - lw;
+        a = 0.5f * dv;
+        return (double)(u * du) + (double)(v * dv);
+    } else {
+        const float d = ph - gh;
+        if constexpr (KIND == 3) {
+            a = (2.0f * pixels) * d;
+            return (double)(d * d);
+        } else {
+            a = d > 0.0f ? 0.5f : (d < 0.0f ? -0.5f : 0.0f);        // (|x| has derivative 0 at 0, as torch's abs)
+            return (double)fabsf(d);
+        }
+    }
+}
+template <int KIND>
+__device__ __forceinline__ double unit_l1_loss_factor(int64_t npix) { return KIND == 3 ? (double)npix : 0.5; }
+
+// gl dL/dp_k of a loss of p^ from a_k = dL/dp^_k and dot = sum_j a_j p_j: the pixel's own part and the part through the norm of p
+// (sign(p_k) dot / dp^2; none when the norm is clamped).  Divided by dp twice: dp^2 would leave fp32 for norms beyond 1e19.
+__device__ __forceinline__ float unit_l1_gradient(const KlNorms& n, float a, float pk, float dotf, float gl)
+{
+    const float sgn = pk > 0.0f ? 1.0f : (pk < 0.0f ? -1.0f : 0.0f);
+    const float through_norm = n.npf > KlNorms::eps ? sgn * ((dotf / n.dp) / n.dp) : 0.0f;
+    return gl * (a / n.dp - through_norm);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kReduceBlock) void flux_gain_free_loss_kernel(const float* __restrict__ pred, const float* __restrict__ truth,
+                                                                         int64_t npix, float* __restrict__ loss,
+                                                                         const float* __restrict__ grad_loss,
+                                                                         float* __restrict__ grad_pred)
+{
+    __shared__ double s_red[16 * 3];
+    const int b = blockIdx.x;
+    const float* __restrict__ p = pred + (int64_t)b * npix;
+    const float* __restrict__ g = truth + (int64_t)b * npix;
+    float* __restrict__ gp = grad_pred ? grad_pred + (int64_t)b * npix : nullptr;
+    if constexpr (KIND == 5) {
+        // torch.nn.functional.cosine_similarity (eps = 1e-8): sum (p / max(|p|_2, eps)) (g / max(|g|_2, eps)) - EACH norm is clamped,
+        // and the clamp is applied outside autograd: the gradient goes through |p|_2 as if it were not clamped (0 at p = 0).
+        // The three sums of one pass give the same number: dot / (n1c n2c).
+        constexpr float eps = 1e-8f;
+        double pp = 0.0, gg = 0.0, pg = 0.0;
+        for_each_pair(p, g, npix, [&](int64_t, float pk, float gk) { pp += (double)(pk * pk); gg += (double)(gk * gk); pg += (double)(pk * gk); });
+        double s[3] = {pp, gg, pg};
+        block_sum_n<3>(s, s_red);
+        const float n1 = (float)sqrt(s[0]), n2 = (float)sqrt(s[1]);
+        const float n1c = fmaxf(n1, eps), n2c = fmaxf(n2, eps);
+        const float c = (float)s[2] / (n1c * n2c);
+        if (threadIdx.x == 0 && loss) loss[b] = 1.0f - c;
+        if (gp) {
+            // d(1 - c)/dp_k = -(g_k / n2c - c p_k / |p|_2) / n1c
+            const float gl = grad_loss[b];
+            for_each_pair(p, g, npix, [&](int64_t k, float pk, float gk) {
+                const float along = n1 > 0.0f ? pk / n1 : 0.0f;
+                gp[k] = -gl * ((gk / n2c - c * along) / n1c);
+            });
+        }
+    } else {
+        double np_ = 0.0, ng = 0.0;
+        for_each_pair(p, g, npix, [&](int64_t, float pk, float gk) { np_ += (double)fabsf(pk); ng += (double)fabsf(gk); });
+        double norms[2] = {np_, ng};
+        block_sum_n<2>(norms, s_red);
+        const KlNorms n((float)norms[0], (float)norms[1]);
+        const float pixels = (float)npix;
+        double acc = 0.0, dot = 0.0;
+        for_each_pair(p, g, npix, [&](int64_t, float pk, float gk) {
+            float a;
+            acc += unit_l1_pixel<KIND>(pk / n.dp, gk / n.dg, pixels, a);
+            dot += (double)(a * pk);
+        });
+        double s[2] = {acc, dot};
+        block_sum_n<2>(s, s_red);
+        const float dotf = (float)s[1];
+        if (threadIdx.x == 0 && loss) loss[b] = (float)(s[0] * unit_l1_loss_factor<KIND>(npix));
+        if (gp) {
+            const float gl = grad_loss[b];
+            for_each_pair(p, g, npix, [&](int64_t k, float pk, float gk) {
+                float a;
+                unit_l1_pixel<KIND>(pk / n.dp, gk / n.dg, pixels, a);
+                gp[k] = unit_l1_gradient(n, a, pk, dotf, gl);
+            });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The fused crop + PixelLoss pair.  A bitmap's rows are ALWAYS summed in kLossParts = 4 parts, whatever the batch size: the
 // parts' fp64 sums (per-thread order, block tree) are added in part order, so the loss, the centre and the gradient are the
 // same bits whether a bitmap has one workgroup (large batches: all four parts in one workgroup, one launch) or two / four
@@ -851,12 +955,24 @@ extern "C" int art_flux_loss(const float* prediction, const float* ground_truth,
                              float* loss, const float* grad_loss, float* grad_prediction, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (empty_batch(B, npix, 1) && (kind == 0 || kind == 1)) return ART_OK;
-    if (!prediction || !ground_truth || B < 0 || npix < 1 || (kind != 0 && kind != 1) || (!loss && !grad_prediction) ||
+    const bool known_kind = kind >= 0 && kind <= 5;
+    if (empty_batch(B, npix, 1) && known_kind) return ART_OK;
+    if (!prediction || !ground_truth || B < 0 || npix < 1 || !known_kind || (!loss && !grad_prediction) ||
         (grad_prediction && !grad_loss))
         return ART_EINVAL;
-    hipLaunchKernelGGL(flux_loss_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, prediction, ground_truth, npix,
-                       kind, loss, grad_loss, grad_prediction);
+    auto gain_free = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, prediction, ground_truth, npix, loss, grad_loss,
+                           grad_prediction);
+    };
+    switch (kind) {
+    case 2: gain_free(flux_gain_free_loss_kernel<2>); break;
+    case 3: gain_free(flux_gain_free_loss_kernel<3>); break;
+    case 4: gain_free(flux_gain_free_loss_kernel<4>); break;
+    case 5: gain_free(flux_gain_free_loss_kernel<5>); break;
+    default:
+        hipLaunchKernelGGL(flux_loss_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, prediction, ground_truth, npix,
+                           kind, loss, grad_loss, grad_prediction);
+    }
     ART_HIP(hipGetLastError());
     return ART_OK;
 }

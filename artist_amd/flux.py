@@ -320,6 +320,8 @@ def _check_reduction(kwargs: dict, what: str) -> None:
         if what == "pixel":
             raise ValueError("The vector loss expects ['reduction_dimensions'] as keyword arguments. "
                              "Please add 'reduction_dimensions' as keyword argument.")
+        if what != "kl":                                # a gain-invariant loss (the reference has none): named in full
+            raise ValueError(f"The {what} loss expects 'reduction_dimensions' as keyword argument. Please add this argument.")
         raise ValueError("The KL-divergence loss expects 'reduction_dimensions' as keyword argument. "
                          "Please add this argument.")
     if tuple(int(d) for d in kwargs["reduction_dimensions"]) not in ((1, 2), (-2, -1)):
@@ -341,3 +343,44 @@ class KLDivergenceLoss:
     def __call__(self, prediction: torch.Tensor, ground_truth: torch.Tensor, **kwargs: Any) -> torch.Tensor:
         _check_reduction(kwargs, "kl")
         return _FluxLoss.apply(prediction, ground_truth, 1)
+
+
+# The gain-invariant losses (no counterpart in the reference): a measured flux image is a camera frame whose
+# gain against the traced flux is unknown, so these compare SHAPES - multiplying the prediction or the ground truth by a
+# positive number changes none of them - and, unlike the KL divergence, all four are bounded.
+class JensenShannonLoss:
+    """Jensen-Shannon divergence of the L1-normalised bitmaps per sample (``art_flux_loss`` kind 2), in about ``[0, ln 2]``:
+    ``1/2 D_KL(g^ || m) + 1/2 D_KL(p^ || m)`` with ``m = (p^ + g^) / 2`` and the ``+ 1e-12`` of ``KLDivergenceLoss`` inside every
+    logarithm.  A prediction that is empty costs about ``ln(2) / 2`` where the KL divergence costs about 27.6."""
+
+    def __call__(self, prediction: torch.Tensor, ground_truth: torch.Tensor, **kwargs: Any) -> torch.Tensor:
+        _check_reduction(kwargs, "Jensen-Shannon")
+        return _FluxLoss.apply(prediction, ground_truth, 2)
+
+
+class ShapePixelLoss:
+    """``PixelLoss`` of the two bitmaps each scaled to unit mean, per sample (``art_flux_loss`` kind 3):
+    ``K sum (p^ - g^)^2`` for bitmaps of ``K`` pixels, ``p^`` and ``g^`` L1-normalised."""
+
+    def __call__(self, prediction: torch.Tensor, ground_truth: torch.Tensor, **kwargs: Any) -> torch.Tensor:
+        _check_reduction(kwargs, "shape pixel")
+        return _FluxLoss.apply(prediction, ground_truth, 3)
+
+
+class TotalVariationLoss:
+    """Total variation distance of the L1-normalised bitmaps per sample (``art_flux_loss`` kind 4): ``1/2 sum |p^ - g^|`` in
+    ``[0, 1]``, the share of the flux that lies in the wrong place."""
+
+    def __call__(self, prediction: torch.Tensor, ground_truth: torch.Tensor, **kwargs: Any) -> torch.Tensor:
+        _check_reduction(kwargs, "total variation")
+        return _FluxLoss.apply(prediction, ground_truth, 4)
+
+
+class CosineFluxLoss:
+    """One minus the cosine similarity of the flattened bitmaps per sample (``art_flux_loss`` kind 5): what
+    ``artist_amd.losses.CosineSimilarityLoss`` gives on ``prediction.flatten(1)``, ``ground_truth.flatten(1)``, in one pass over
+    the bitmaps."""
+
+    def __call__(self, prediction: torch.Tensor, ground_truth: torch.Tensor, **kwargs: Any) -> torch.Tensor:
+        _check_reduction(kwargs, "cosine flux")
+        return _FluxLoss.apply(prediction, ground_truth, 5)

@@ -3,7 +3,7 @@
 Drop-ins for ``artist.optim.loss.VectorLoss``, ``AngleLoss`` and ``CosineSimilarityLoss`` (artist/optim/loss.py:61-121, 413-506):
 called as ``loss(prediction, ground_truth, **kwargs)`` on ``[samples, 4]`` tensors, one value per sample.  A handful of torch ops
 on a few floats per sample, on whichever device the arguments live (like ``artist_amd.flux_integral_constraint``); the flux
-losses, which read whole bitmaps, are the fused ones of ``artist_amd.flux``.
+losses, which read whole bitmaps, are the fused ones of ``artist_amd.flux``; its four gain-invariant ones are exported here too.
 """
 from __future__ import annotations
 
@@ -11,7 +11,10 @@ from typing import Any
 
 import torch
 
-__all__ = ["VectorLoss", "AngleLoss", "CosineSimilarityLoss"]
+from .flux import CosineFluxLoss, JensenShannonLoss, ShapePixelLoss, TotalVariationLoss  # noqa: F401  (the gain-invariant flux losses)
+
+__all__ = ["VectorLoss", "AngleLoss", "CosineSimilarityLoss", "JensenShannonLoss", "ShapePixelLoss", "TotalVariationLoss",
+           "CosineFluxLoss"]
 
 
 class VectorLoss:

@@ -11,18 +11,21 @@ reference has them (``artist.optim``), and so are ``AimPointOptimizer`` (``artis
 ``SurfaceReconstructor`` (``artist_amd.surface_reconstructor``; with ``parameters=(...)`` it hands this ``Adam`` one parameter
 group per learnable tensor - control points, facet canting, facet translations), ``KinematicsReconstructor``
 (``artist_amd.kinematics_reconstructor``; with ``parameters=(...)``, drawn from ``KINEMATICS_PARAMETER_NAMES``, one parameter
-group per learnable tensor as well - rotation deviations, translation deviations, actuator parameters) and the losses on vectors it compares normals with (``artist_amd.losses``).
+group per learnable tensor as well - rotation deviations, translation deviations, actuator parameters) and the losses on vectors it compares normals with (``artist_amd.losses``), and
+the gain-invariant flux losses of ``artist_amd.flux`` (``JensenShannonLoss``, ``ShapePixelLoss``, ``TotalVariationLoss``, ``CosineFluxLoss``).
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
-from .losses import AngleLoss, CosineSimilarityLoss, VectorLoss
+from .losses import (AngleLoss, CosineFluxLoss, CosineSimilarityLoss, JensenShannonLoss, ShapePixelLoss, TotalVariationLoss,
+                     VectorLoss)
 from .regularizers import IdealSurfaceRegularizer, SmoothnessRegularizer
 
 __all__ = ["Adam", "AimPointOptimizer", "SurfaceReconstructor", "KinematicsReconstructor", "SmoothnessRegularizer",
-           "IdealSurfaceRegularizer", "VectorLoss", "AngleLoss", "CosineSimilarityLoss", "KINEMATICS_PARAMETER_NAMES"]
+           "IdealSurfaceRegularizer", "VectorLoss", "AngleLoss", "CosineSimilarityLoss", "KINEMATICS_PARAMETER_NAMES",
+           "JensenShannonLoss", "ShapePixelLoss", "TotalVariationLoss", "CosineFluxLoss"]
 
 
 class Adam(torch.optim.Optimizer):

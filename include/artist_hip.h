@@ -330,6 +330,22 @@ int art_flux_crop_bwd(const float *flux, const float *target_dims, const float *
 /* ---------------------------------------------------------------------------------------------
  * art_flux_loss - PixelLoss (kind 0, artist/optim/loss.py:251-318: sum (p-g)^2 / sum g) or KLDivergenceLoss
  * (kind 1, :321-410: L1-normalise both, KLDivLoss(log_target) on log(. + 1e-12)), reduced over the bitmap.
+ * Kinds 2 to 5 have no counterpart among the reference's flux losses: they do not depend on the gain of either bitmap
+ * (a measured flux image is a camera frame of unknown gain) and, unlike kind 1, they are bounded.  Per bitmap of
+ * K = npix pixels, eps = 1e-12, p^ = p / max(sum |p|, eps), g^ = g / max(sum |g|, eps) - the norms and clamps of kind 1:
+ *   kind 2  Jensen-Shannon: m = (p^ + g^) / 2,
+ *           1/2 sum (g^ + eps)(log(g^ + eps) - log(m + eps)) + 1/2 sum (p^ + eps)(log(p^ + eps) - log(m + eps)),
+ *           about [0, ln 2]; an empty prediction costs about ln(2) / 2 (kind 1: about 27.6)
+ *   kind 3  shape pixel loss: K sum (p^ - g^)^2 - PixelLoss of the two bitmaps each scaled to unit mean
+ *   kind 4  total variation: 1/2 sum |p^ - g^| in [0, 1]; the derivative of |x| at 0 is 0
+ *   kind 5  cosine: 1 - sum (p / max(|p|_2, 1e-8)) (g / max(|g|_2, 1e-8)) over the flattened bitmap, no L1 normalisation:
+ *           CosineSimilarityLoss (:462-506) on [B,K] inputs, i.e. torch.nn.functional.cosine_similarity(eps = 1e-8), which
+ *           clamps EACH norm at eps (not their product) and applies the clamp outside autograd: the gradient goes through
+ *           |p|_2 as if it were not clamped, and is g / (max(|g|_2, eps) eps) at p = 0
+ * The gradient w.r.t. the prediction is what autograd derives from these formulas; for kinds 2 to 4 it includes the path
+ * through the norm of p with sign(p_k), and none when sum |p| <= eps.  The ground truth gets no gradient.  One workgroup
+ * per bitmap, fp64 sums in a fixed order, no atomics: a bitmap's bits depend on neither B nor the run.
+ * B == 0 is ART_OK for kinds 0 to 5 (the pointers are not looked at); any other kind is ART_EINVAL.
  *   prediction, ground_truth [B,npix]; loss [B] out (may be NULL in a backward-only call);
  *   grad_loss [B] + grad_prediction [B,npix] out: both NULL for forward only.
  * ------------------------------------------------------------------------------------------- */

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""The flux epilogue's ten entry points (artist_amd/csrc/flux_kernels.hip), timed or compared bit for bit between builds.
+"""The flux epilogue's ten entry points (artist_amd/csrc/flux_kernels.hip; art_flux_loss at each of its six kinds), timed or compared
+bit for bit between builds.
 
 Timing: bitmaps of 256 x 256 (default 1000, the metric field; 125 is one rank's share), every library loaded into ONE process and
 timed in interleaved rounds - boxes differ by 10-20 % on the same binary, so only numbers of one run compare.  Per library and
-call: median and minimum over the rounds, and the algorithmic HBM rate of the median (one read + one write of the bitmaps, two
+call: median, minimum and maximum over the rounds, and the algorithmic HBM rate of the median (one read + one write of the bitmaps, two
 reads for kernels with two inputs).  One JSON line per bitmap count.
 
 --bits A=lib.so B=lib.so: every entry point of the two libraries on the inputs of tests/flux_ref.py (all of CASES) and on the metric
@@ -72,7 +73,7 @@ def make_calls(inp, crop_w, crop_h):
     calls = [("crop_fwd", lambda L: L.art_flux_crop_fwd(p(flux), p(dims), B, Hh, W, cw, ch, p("crop"), p("centers"), s), ["crop", "centers"], 2 * n),
              ("crop_bwd", lambda L: L.art_flux_crop_bwd(p(flux), p(dims), p("centers"), B, Hh, W, cw, ch, p(gout), p("grad_flux"), p("crop_ws"), s),
               ["grad_flux", "crop_ws"], 3 * n)]
-    for kind, tag in ((0, "pixel"), (1, "kl")):
+    for kind, tag in ((0, "pixel"), (1, "kl"), (2, "jensen_shannon"), (3, "shape_pixel"), (4, "total_variation"), (5, "cosine")):
         calls += [(f"{tag}_loss_fwd", lambda L, kind=kind: L.art_flux_loss(p("crop"), p(truth), B, Hh * W, kind, p("loss"), None, None, s), ["loss"], 2 * n),
                   (f"{tag}_loss_bwd", lambda L, kind=kind: L.art_flux_loss(p("crop"), p(truth), B, Hh * W, kind, None, p(gl), p("grad_pred"), s),
                    ["grad_pred"], 3 * n)]
@@ -122,7 +123,8 @@ def time_variants(variants, B, rounds, steps):
         for name, _, _, alg in calls:
             t = times[(vname, name)]
             med = statistics.median(t)
-            out[vname][name] = {"ms": round(med, 4), "min_ms": round(min(t), 4), "algorithmic_GBps": round(alg / med / 1e6, 1),
+            out[vname][name] = {"ms": round(med, 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4),
+                                "algorithmic_GBps": round(alg / med / 1e6, 1),
                                 "frac_of_8TBps": round(alg / med / 1e6 / 8000, 3)}
     return {"bitmaps": B, "resolution": [256, 256], "rounds": rounds, "steps": steps, "variants": out}
 
@@ -145,6 +147,9 @@ def compare_bits(variants):
                 os.environ["ARTIST_HIP_LOSS_PARTS"] = parts
             for name, fn, outs, _ in calls:         # (a later call reads the records library B left: equal ones if all is well)
                 if parts is not None and not name.startswith("crop_pixel_loss"):
+                    continue
+                if _lib.ART_EINVAL in [fn(lib) for lib in (la, lb)]:     # a loss kind that an older build does not know
+                    report.append({"case": shape, "parts": parts or "unset", "call": name, "buffer": None, "verdict": "not in both libraries"})
                     continue
                 got = []
                 for lib in (la, lb):
