@@ -109,13 +109,20 @@ __global__ __launch_bounds__(kAlignBlock) void reflect_kernel(const float4* __re
 
 using namespace art;
 
+// The kernels of this file read and write their [.,.,4] tensors as float4: a pointer that is not 16-byte aligned (a contiguous
+// view at a storage offset of one float) is refused here, before anything is launched.  The [H,4,4] orientation table is read
+// as scalars and is exempt; reflect_kernel reads its [H,4] incident rows as float4 too, so art_reflect holds them to the rule.
+static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
 extern "C" int art_reflect(const float* incident, const float* normals, int64_t H, int64_t P, float* out, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (H < 0 || P < 0) return ART_EINVAL;
     if (H == 0 || P == 0) return ART_OK;
     const int64_t total = H * P;
-    if (!incident || !normals || !out || (total + kAlignBlock - 1) / kAlignBlock > 2147483647LL) return ART_EINVAL;
+    if (!incident || !normals || !out || misaligned16(incident) || misaligned16(normals) || misaligned16(out) ||
+        (total + kAlignBlock - 1) / kAlignBlock > 2147483647LL)
+        return ART_EINVAL;
     hipLaunchKernelGGL(reflect_kernel, dim3((unsigned)((total + kAlignBlock - 1) / kAlignBlock)), dim3(kAlignBlock), 0, stream,
                        reinterpret_cast<const float4*>(incident), reinterpret_cast<const float4*>(normals), P, total,
                        reinterpret_cast<float4*>(out));
@@ -127,11 +134,12 @@ extern "C" int art_align_fwd(const float* points, const float* normals, const fl
                              int64_t P, float* out_points, float* out_normals, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (H == 0) return ART_OK;
-    if (!points || !normals || !orientation || !out_points || !out_normals || H < 0 || P <= 0 || P > 2147483647LL ||
-        H * ((P + kAlignBlock - 1) / kAlignBlock) > 2147483647LL)
+    if (H < 0 || P < 0) return ART_EINVAL;
+    if (H == 0 || P == 0) return ART_OK;                  // an empty batch, like the bmm this replaces: nothing to write
+    if (!points || !normals || !orientation || !out_points || !out_normals || P > 2147483647LL ||
+        H * ((P + kAlignBlock - 1) / kAlignBlock) > 2147483647LL || misaligned16(points) || misaligned16(normals) ||
+        misaligned16(out_points) || misaligned16(out_normals))
         return ART_EINVAL;
-    if (H == 0) return ART_OK;
     const int n_tiles = (int)((P + kAlignBlock - 1) / kAlignBlock);
     hipLaunchKernelGGL(align_fwd_kernel, dim3((unsigned)(H * n_tiles)), dim3(kAlignBlock), 0, stream,
                        reinterpret_cast<const float4*>(points), reinterpret_cast<const float4*>(normals), orientation,
@@ -146,12 +154,18 @@ extern "C" int art_align_bwd(const float* points, const float* normals, const fl
                              float* grad_points, float* grad_normals, float* grad_orientation, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (H < 0 || P < 0) return ART_EINVAL;
     if (H == 0) return ART_OK;
-    if (!orientation || !grad_out_points || !grad_out_normals || !grad_points || !grad_normals || H < 0 || P <= 0 ||
+    if (P == 0) {                                         // empty heliostats: the sum over no points, still fully written
+        if (grad_orientation) ART_HIP(hipMemsetAsync(grad_orientation, 0, (size_t)H * 16 * sizeof(float), stream));
+        return ART_OK;
+    }
+    if (!orientation || !grad_out_points || !grad_out_normals || !grad_points || !grad_normals ||
         P > 2147483647LL || H * ((P + kAlignBlock - 1) / kAlignBlock) > 2147483647LL ||
-        (grad_orientation && (!points || !normals)))
+        (grad_orientation && (!points || !normals)) || misaligned16(grad_out_points) || misaligned16(grad_out_normals) ||
+        misaligned16(grad_points) || misaligned16(grad_normals) ||
+        (grad_orientation && (misaligned16(points) || misaligned16(normals))))
         return ART_EINVAL;
-    if (H == 0) return ART_OK;
     const int n_tiles = (int)((P + kAlignBlock - 1) / kAlignBlock);
     const dim3 grid((unsigned)(H * n_tiles));
     hipLaunchKernelGGL(align_bwd_kernel, grid, dim3(kAlignBlock), 0, stream, orientation,

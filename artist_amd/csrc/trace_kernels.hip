@@ -3876,7 +3876,11 @@ extern "C" int art_per_target_sum(const float* bitmaps, const int32_t* target_id
                                   int64_t npix, float* out, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!out || T <= 0 || npix <= 0 || H < 0 || T > 65535 || (H > 0 && (!bitmaps || !target_idx))) return ART_EINVAL;
+    if (T < 0 || npix < 0 || H < 0) return ART_EINVAL;
+    if (T == 0 || npix == 0) return ART_OK;              // an empty output: nothing to write
+    if (!out || H > 2147483647LL || T > 65535 || (H > 0 && (!bitmaps || !target_idx)) ||
+        (npix + 255) / 256 > 2147483647LL)               // (the kernels count heliostats in an int; one block per 256 pixels)
+        return ART_EINVAL;
     const bool vec4 = npix >= (int64_t)1 << 20 && (npix % 4) == 0 && (reinterpret_cast<uintptr_t>(bitmaps) % 16) == 0 &&
                       (reinterpret_cast<uintptr_t>(out) % 16) == 0;
     if (vec4)

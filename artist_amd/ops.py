@@ -74,6 +74,13 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def _f32c16(t: torch.Tensor) -> torch.Tensor:
+    """``_f32c`` whose first element is 16-byte aligned as well: the align and reflect kernels move [4] rows as float4 and their
+    entry points refuse a pointer that is not (a contiguous view at a storage offset of one float); such a view is copied."""
+    t = _f32c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 # Small per-call conversions that an optimisation loop repeats with the SAME tensors every epoch - the int32 copy of the
 # target indices, the [H,F,K] materialisation of an expanded knot vector - are kept (sixteen entries of a few KB).  Each is a
 # 5 us kernel that a 1 ms epoch of a rank's share of a field would pay several times over.
@@ -161,7 +168,7 @@ def reflect_directions(incident: torch.Tensor, normals: torch.Tensor) -> torch.T
     """``incident[h] - 2 (incident[h] . normals[h,p]) normals[h,p]`` for ``incident [H,4]``, ``normals [H,P,4]``
     (``art_reflect``; artist/raytracing/geometry.py:11-41).  Not differentiable."""
     dev = _require_cuda(incident, normals)
-    incident, normals = _f32c(incident.detach()), _f32c(normals.detach())
+    incident, normals = _f32c16(incident.detach()), _f32c16(normals.detach())
     H, P = int(normals.shape[0]), int(normals.shape[1])
     if incident.shape != (H, 4) or normals.shape != (H, P, 4):
         raise ValueError("incident must be [H,4] and normals [H,P,4]")
@@ -767,7 +774,7 @@ class AlignSurfaces(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, normals, orientation):
         dev = _require_cuda(points, normals, orientation)
-        points, normals, orientation = _f32c(points), _f32c(normals), _f32c(orientation)
+        points, normals, orientation = _f32c16(points), _f32c16(normals), _f32c(orientation)
         H, P = points.shape[0], points.shape[1]
         if points.shape != (H, P, 4) or normals.shape != (H, P, 4) or orientation.shape != (H, 4, 4):
             raise ValueError("points/normals must be [H,P,4] and orientation [H,4,4]")
@@ -783,7 +790,7 @@ class AlignSurfaces(torch.autograd.Function):
         points, normals, orientation = ctx.saved_tensors
         dev = points.device
         H, P = points.shape[0], points.shape[1]
-        g_out_p, g_out_n = _f32c(g_out_p), _f32c(g_out_n)
+        g_out_p, g_out_n = _f32c16(g_out_p), _f32c16(g_out_n)
         g_p, g_n = torch.empty_like(points), torch.empty_like(normals)
         g_m = torch.empty_like(orientation) if ctx.needs_input_grad[2] else None
         _lib.call("art_align_bwd", dev, points.data_ptr(), normals.data_ptr(), orientation.data_ptr(),

@@ -232,6 +232,11 @@ int art_blocking_filter(const float *origins, const float *normals, const float 
  * art_per_target_sum - HeliostatRayTracer.get_bitmaps_per_target
  * (heliostat_ray_tracer.py:563-608): out[t] = sum of bitmaps[h] with target_idx[h] == t.
  *   bitmaps [H,npix], target_idx [H], out [T,npix] (fully written).
+ *   Heliostats are added in index order; an index outside [0, T) contributes nothing.  T <= 65535; T == 0 or npix == 0 is
+ *   an empty output (ART_OK, no pointer is looked at); H == 0 zero-fills out.
+ *   0 <= H <= INT_MAX (the kernels count heliostats in an int: a larger H is refused with ART_EINVAL, never narrowed).
+ *   Bitmaps of 2^20 pixels and more are summed four pixels per thread when npix % 4 == 0 and bitmaps and out are 16-byte
+ *   aligned, one pixel per thread otherwise: the same bits either way.
  * ------------------------------------------------------------------------------------------- */
 int art_per_target_sum(const float *bitmaps, const int32_t *target_idx, int64_t H, int64_t T, int64_t npix,
                        float *out, void *stream);
@@ -274,6 +279,9 @@ int art_nurbs_bwd(const float *control_points, const float *eval_points, int64_t
  * `heliostat_group.preferred_reflection_directions`, which HeliostatRayTracer.trace_rays publishes on every call
  * (artist/raytracing/heliostat_ray_tracer.py:285-290).
  *   incident [H,4], normals [H,P,4], out [H,P,4]
+ *   Alignment: the kernel moves whole [4] rows as 16-byte accesses, so incident, normals and out must be 16-byte aligned; a
+ *   pointer that is not (a contiguous view at a storage offset of one float) is refused with ART_EINVAL before anything is
+ *   launched.  H == 0 or P == 0: nothing to do, ART_OK without looking at a pointer.
  * ------------------------------------------------------------------------------------------- */
 int art_reflect(const float *incident, const float *normals, int64_t H, int64_t P, float *out, void *stream);
 
@@ -299,6 +307,12 @@ int art_adam_step(float *param, const float *grad, float *exp_avg, float *exp_av
  * art_align_bwd - its autograd: grad_points = g @ orientation (same for normals) and, when
  *   grad_orientation != NULL, grad_orientation[h] = sum_p (g_points^T x_points + g_normals^T x_normals)
  *   ([H,4,4], fully written) - the path by which kinematic parameters receive gradients.
+ *   Alignment: every [H,P,4] tensor of both calls (inputs, upstream gradients, outputs) is moved as 16-byte accesses and must
+ *   be 16-byte aligned; a pointer that is not is refused with ART_EINVAL before anything is launched.  The orientation
+ *   table and grad_orientation are accessed as scalars and are exempt.
+ *   Empty batches: H == 0 or P == 0 is accepted like the batched matmul this replaces (ART_OK, no pointer of an [H,P,4]
+ *   tensor is looked at and the forward launches nothing); art_align_bwd with P == 0 still fully writes grad_orientation
+ *   - the sum over no points - with zeros.
  * ------------------------------------------------------------------------------------------- */
 int art_align_fwd(const float *points, const float *normals, const float *orientation, int64_t H, int64_t P,
                   float *out_points, float *out_normals, void *stream);
