@@ -18,13 +18,15 @@ from __future__ import annotations
 
 import logging
 from dataclasses import dataclass
+from functools import partial
 from typing import Any
 
 import torch
 
-from . import _lib, distributed, optics, training
+from . import distributed, optics, training
 from .flux import JensenShannonLoss, KLDivergenceLoss
 from .raytracing import HeliostatRayTracer
+from .reconstruction import gpu_device, scheduler_and_stopper
 
 log = logging.getLogger(__name__)
 
@@ -114,12 +116,7 @@ def _require_kl(loss_definition) -> None:
                         "other loss definition there is no loss to differentiate")
 
 
-def _gpu_device(device) -> torch.device:
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
-    device = torch.device("cpu") if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise _lib.ArtistHipError(f"AimPointOptimizer runs on the GPU only (device {device}); there is no CPU fallback")
-    return device
+_gpu_device = partial(gpu_device, who="AimPointOptimizer")
 
 
 class AimPointOptimizer:
@@ -206,11 +203,7 @@ class AimPointOptimizer:
         self.number_of_heliostats = offset
 
         self.optimizer = Adam([g["parameter"] for g in self.groups], lr=float(self.optimizer_dict["initial_learning_rate"]))
-        self.scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=self.optimizer,
-                                                                                 parameters=self.scheduler_dict)
-        self.early_stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
-                                                    patience=self.optimizer_dict["early_stopping_patience"],
-                                                    min_improvement=self.optimizer_dict["early_stopping_delta"], relative=True)
+        self.scheduler, self.early_stopper = scheduler_and_stopper(self.optimizer, self.optimizer_dict, self.scheduler_dict)
         pixels = self._resolution_host[0] * self._resolution_host[1]
         allowed = torch.prod(self._target_plane_dimensions().to(device)) / pixels * float(self.constraint_dict["max_flux_density"])
         self.state = ConstraintState.fresh(self.constraint_dict, allowed, self.epsilon)
@@ -320,10 +313,7 @@ class AimPointOptimizer:
                     loss, flux_loss, local_term, intercept_term, integral_term,
                     100 / reference * (total_flux.sum() - reference + 1e-8))]).tolist()
             loss_host = scalars[0]
-            if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
-                scheduler.step(loss_host)
-            else:
-                scheduler.step()
+            training.step_scheduler(scheduler, loss_host)
             if log_step and epoch % log_step == 0 and rank == 0:
                 log.info(f"Epoch: {epoch}, Loss: {loss_host}, LR: {optimizer.param_groups[0]['lr']}")
             for key, value in zip(HISTORY_KEYS, scalars):

@@ -39,17 +39,15 @@ More than one rank has not run on a GPU: the collectives (``_synchronize_gradien
 from __future__ import annotations
 
 import logging
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from functools import partial
 from typing import Any
 
 import torch
 
-from . import _lib, distributed, training
-from ._memo import Memo
 from .flux import FocalSpotLoss, KLDivergenceLoss, PixelLoss
 from .raytracing import HeliostatRayTracer
-from .surface_reconstructor import LearnsParameters, learning_rates, tensors_held_by
+from .reconstruction import ReconstructionGroupState, Reconstructor
 from .training import reduce_loss_per_sample
 
 log = logging.getLogger(__name__)
@@ -86,29 +84,12 @@ class KinematicsEpochLoss:
 
 
 @dataclass
-class KinematicsGroupState:
-    """What the epochs of one heliostat group share (``KinematicsReconstructor.prepare``)."""
-    index: int
-    group: Any
-    mask: torch.Tensor
-    split: training.TrainTestSplit
-    active_rows: torch.Tensor                   # group-local rows of the heliostats that have samples, [active] on the device
-    optimizer: torch.optim.Optimizer
-    scheduler: Any
-    early_stopper: training.EarlyStopping
+class KinematicsGroupState(ReconstructionGroupState):
+    """What the epochs of one heliostat group share (``KinematicsReconstructor.prepare``), beside the fields every
+    reconstruction has; ``learnables`` are the kinematics' own tensors."""
     normals_measured: torch.Tensor | None = None    # alignment mode: of all samples, [samples, 4]
     normals_measured_train: torch.Tensor | None = None
-    activated: str | None = None                # "train" / "test": which samples the group is activated for
     surfaces: tuple | None = None               # the activated samples' surface points and normals before alignment
-    tracers: dict = field(default_factory=dict)
-    rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
-    # this rank's rows of the per-sample tensors (_own): flux and targets of the training samples
-    own: Memo = field(default_factory=lambda: Memo("this rank's rows of a per-sample tensor", capacity=8, under_capture="serve"))
-    # epoch_graph: the captured training step and what is kept alive for it
-    graph: Any = None
-    kept: list = field(default_factory=list)
-    # what learns: name -> the kinematics' own tensor, in the canonical order (KINEMATICS_PARAMETER_NAMES)
-    learnables: dict = field(default_factory=dict)
 
 
 def _slot(kinematics, name: str) -> tuple:
@@ -119,15 +100,7 @@ def _slot(kinematics, name: str) -> tuple:
     return kinematics, stem, "active_" + stem
 
 
-def _gpu_device(device) -> torch.device:
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
-    device = torch.device("cpu") if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise _lib.ArtistHipError(f"KinematicsReconstructor runs on the GPU only (device {device}); there is no CPU fallback")
-    return device
-
-
-class KinematicsReconstructor(LearnsParameters):
+class KinematicsReconstructor(Reconstructor):
     """``artist.optim.KinematicsReconstructor``: see the module docstring; attributes as in the reference (:38-60).
 
     ``prepare`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_kinematics`` runs per group, for callers that step
@@ -158,7 +131,7 @@ class KinematicsReconstructor(LearnsParameters):
                  dni: float | None = None, reconstruction_method: str = KINEMATICS_RECONSTRUCTION_RAYTRACING,
                  bitmap_resolution: torch.Tensor = torch.tensor([256, 256]), device: torch.device | None = None,
                  epoch_graph: bool = False) -> None:
-        _gpu_device(device)
+        self._device(device)
         if ddp_setup["rank"] == 0:
             log.info("Create a kinematics reconstructor.")
         self.ddp_setup = ddp_setup
@@ -178,6 +151,8 @@ class KinematicsReconstructor(LearnsParameters):
         self.epoch_graph = bool(epoch_graph)
 
     PARAMETER_NAMES = KINEMATICS_PARAMETER_NAMES        # (the rotation deviations alone, unless chosen otherwise)
+    HISTORY_KEYS = ("total_loss",)
+    RECONSTRUCTS = "kinematics"
 
     @property
     def _flux_driven(self) -> bool:
@@ -190,8 +165,7 @@ class KinematicsReconstructor(LearnsParameters):
         ``artist_amd.optim.Adam`` with one parameter group per tensor of ``self.parameters`` (``requires_grad_()`` on those, and on
         no other; ``state.learnables``), the configured scheduler and early stopping.  A ``ValueError`` for a choice that cannot
         be learned (the class docstring).  None for a group without samples."""
-        from .optim import Adam
-        device = _gpu_device(device)
+        device = self._device(device)
         if "translation_deviations" in self.parameters and not self._flux_driven:
             raise ValueError("'translation_deviations' cannot be learned with reconstruction_method='alignment': the predicted "
                              "normal is the third column of the orientation, translations do not enter it, and their gradient "
@@ -200,27 +174,15 @@ class KinematicsReconstructor(LearnsParameters):
         if "actuator_parameters" in self.parameters and group.kinematics.actuators.optimizable_parameters.numel() == 0:
             raise ValueError(f"'actuator_parameters' cannot be learned on heliostat group {heliostat_group_index}: its actuators "
                              f"are ideal, actuators.optimizable_parameters is empty")
-        flux_measured, focal_spots, incident, motor_positions, mask, targets = self.data["data_parser"].parse_data_for_reconstruction(
-            heliostat_data_mapping=self.data["heliostat_data_mapping"], heliostat_group=group, scenario=self.scenario,
-            bitmap_resolution=self.bitmap_resolution, device=device)
-        active_rows = torch.nonzero(mask > 0, as_tuple=True)[0]
-        if active_rows.numel() == 0:
+        parsed = self._parse_and_split(heliostat_group_index, device)
+        if parsed is None:
             return None
-        split = training.train_test_split(active_heliostats_mask=mask, flux_measured=flux_measured, focal_spots_measured=focal_spots,
-                                          incident_ray_directions=incident, motor_positions=motor_positions,
-                                          target_area_indices=targets, device=device)
-        kinematics = group.kinematics
-        rates = learning_rates(self.optimizer_dict, self.parameters, KINEMATICS_LEARNING_RATE_KEYS)
+        (_, focal_spots, incident, _, mask, _), split, active_rows = parsed
         learnables = {}
         for name in self.parameters:
-            holder, attribute, _ = _slot(kinematics, name)
+            holder, attribute, _ = _slot(group.kinematics, name)
             learnables[name] = getattr(holder, attribute)
-        optimizer = Adam([dict(params=[tensor.requires_grad_()], lr=rates[name]) for name, tensor in learnables.items()],
-                         lr=float(self.optimizer_dict["initial_learning_rate_rotation_deviation"]))
-        scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=optimizer, parameters=self.scheduler_dict)
-        stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
-                                         patience=self.optimizer_dict["early_stopping_patience"],
-                                         min_improvement=self.optimizer_dict["early_stopping_delta"], relative=True)
+        optimizer, scheduler, stopper = self._optimizer_for(learnables, KINEMATICS_LEARNING_RATE_KEYS)
         state = KinematicsGroupState(index=heliostat_group_index, group=group, mask=mask, split=split, active_rows=active_rows,
                                      optimizer=optimizer, scheduler=scheduler, early_stopper=stopper, learnables=learnables)
         if not self._flux_driven:
@@ -239,31 +201,9 @@ class KinematicsReconstructor(LearnsParameters):
         normals = torch.nn.functional.normalize(to_focal_spot - incident_ray_directions[:, :3], dim=-1)
         return torch.cat((normals, torch.zeros_like(normals[:, :1])), dim=1)
 
-    def _rank_rows(self, state: KinematicsGroupState, device):
-        """``(sample rows, heliostat rows)`` that this rank owns among the group's training samples and among its active
-        heliostats - index tensors on the device, or ``(None, None)`` when it owns all, as every rank does in alignment mode.
-        From the sampler's host list (artist/raytracing/sampling.py:107-157): a heliostat's samples stay together."""
-        if "train" not in state.rows:
-            samples = state.split.number_of_train_samples
-            active = int(state.active_rows.numel())
-            owned = list(range(active * samples))
-            if self._flux_driven:
-                from .sampling import RestrictedDistributedSampler
-                owned = RestrictedDistributedSampler(active * samples, active, self.ddp_setup["heliostat_group_world_size"],
-                                                     self.ddp_setup["heliostat_group_rank"]).rank_indices
-            if owned == list(range(active * samples)):
-                state.rows["train"] = (None, None)
-            else:
-                state.rows["train"] = (torch.tensor(owned, dtype=torch.long, device=device),
-                                       torch.tensor([i // samples for i in owned[::samples]], dtype=torch.long, device=device))
-        return state.rows["train"]
-
-    def _own(self, state: KinematicsGroupState, per_sample: torch.Tensor, device) -> torch.Tensor:
-        """This rank's rows of a per-sample tensor of the training samples; the tensor itself when the rank owns all."""
-        sample_rows, _ = self._rank_rows(state, device)
-        if sample_rows is None:
-            return per_sample
-        return state.own.lookup(per_sample, lambda: per_sample.index_select(0, sample_rows), key="train")
+    def _rank_rows(self, state: KinematicsGroupState, kind: str, device):
+        """As the base's; in alignment mode every rank owns all rows."""
+        return super()._rank_rows(state, kind, device) if self._flux_driven else (None, None)
 
     def _orientations(self, state: KinematicsGroupState, kind: str, device) -> torch.Tensor:
         """The learned tensors -> the orientations of the samples of ``kind``, ``[samples, 4, 4]`` (:506-514, 568-577).  The
@@ -316,12 +256,12 @@ class KinematicsReconstructor(LearnsParameters):
         ``loss_definition`` on the predicted and the measured flux of this rank's training samples, the median over a
         heliostat's samples.  Alignment-driven (:472-533): ``loss_definition(prediction, ground_truth)`` on the predicted and
         the measured normals, the mean over a heliostat's samples.  The total is the mean over the heliostats."""
-        device = _gpu_device(device)
+        device = self._device(device)
         split = state.split
         if self._flux_driven:
             prediction = self._flux(state, "train", device)
-            per_sample = loss_definition(prediction=prediction, ground_truth=self._own(state, split.flux_measured_train, device),
-                                         target_area_indices=self._own(state, split.target_area_indices_train, device),
+            per_sample = loss_definition(prediction=prediction, ground_truth=self._own(state, "train", split.flux_measured_train, device),
+                                         target_area_indices=self._own(state, "train", split.target_area_indices_train, device),
                                          reduction_dimensions=(1, 2), device=device)
             reduction = _median_over_samples
         else:
@@ -337,7 +277,7 @@ class KinematicsReconstructor(LearnsParameters):
         ``{"pixel_loss", "kl_div", "focal_spot_loss"}``, each reduced over a heliostat's test samples - by the median in the
         flux-driven mode, by the mean in the alignment-driven one - ``[active heliostats]`` on the device.  Leaves the group
         activated for the test samples; the next ``epoch_loss`` activates it for training again."""
-        device = _gpu_device(device)
+        device = self._device(device)
         split = state.split
         reduction = _median_over_samples if self._flux_driven else _mean_over_samples
         with torch.no_grad():
@@ -367,142 +307,69 @@ class KinematicsReconstructor(LearnsParameters):
         tables and the unaligned ``state.surfaces``, which ``activate_heliostats`` and a validation rebind and never write,
         the measured normals, the rank's rows), so that a validation is not handed their memory.  The step is not activated
         for training again after a validation.  :meth:`close_epoch_graph` ends it."""
-        from . import graphs
-        device = _gpu_device(device)
+        device = self._device(device)
+        return self._capture(state, loss_definition, device)
 
-        def step():
-            loss = self.epoch_loss(state, loss_definition, device)
-            loss.total.backward()
-            return loss.total.detach(), loss.per_heliostat.detach(), loss.per_sample.detach()
-
-        try:
-            state.graph = graphs.EpochGraph(step, warmup=2, parameters=list(state.learnables.values()), device=device)
-        except BaseException:
-            self.close_epoch_graph(state)
-            raise
-        kinematics = state.group.kinematics
-        state.kept = tensors_held_by(state, state.group, kinematics, getattr(kinematics, "actuators", None))
-        return state.graph
+    def _step(self, state: KinematicsGroupState, loss_definition, device) -> tuple:
+        """``(total loss, loss per heliostat, loss per sample)``, detached."""
+        loss = self.epoch_loss(state, loss_definition, device)
+        loss.total.backward()
+        return loss.total.detach(), loss.per_heliostat.detach(), loss.per_sample.detach()
 
     def close_epoch_graph(self, state: KinematicsGroupState) -> None:
         """Close ``state.graph`` and let go of what was kept for it.  No autograd graph that was built on the graph's stream
         outlives it: what the capture left on the group and its kinematics is detached."""
-        if state.graph is not None:
-            state.graph.close()
-        state.graph, state.kept = None, []
-        group, kinematics = state.group, state.group.kinematics
-        group.active_surface_points, group.active_surface_normals = group.active_surface_points.detach(), group.active_surface_normals.detach()
+        self._release(state)
         for name in state.learnables:
-            holder, _, active_attribute = _slot(kinematics, name)
+            holder, _, active_attribute = _slot(state.group.kinematics, name)
             setattr(holder, active_attribute, getattr(holder, active_attribute).detach())
 
     def _synchronize_gradients_nested_ddp(self, optimizer: torch.optim.Optimizer) -> None:
         """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
         sub-world size (:624-648).  Flux-driven mode only."""
-        ddp = self.ddp_setup
-        if not ddp["is_nested"]:
-            return
         for param_group in optimizer.param_groups:
             for parameter in param_group["params"]:
-                if parameter.grad is not None:
-                    distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
-                    parameter.grad /= ddp["heliostat_group_world_size"]
+                self._nested_mean(parameter.grad)
 
     def _synchronize_reconstruction_across_ranks(self, final_loss_per_heliostat: torch.Tensor, loss_history: list) -> list:
         """Every group's rotation deviations and optimisable actuator parameters - and its translation deviations when they
-        are learned - from the first rank that owns the group, the
-        final losses MIN-reduced (a heliostat another rank reconstructed is ``inf`` here), the histories of all ranks gathered
-        (:650-705).  Returns the histories per rank; ``[loss_history]`` in a single process."""
-        ddp = self.ddp_setup
-        if not ddp["is_distributed"]:
-            return [loss_history]
-        with torch.no_grad():
-            for index, group in enumerate(self.scenario.heliostat_field.heliostat_groups):
-                source = ddp["ranks_to_groups_mapping"][index][0]
-                torch.distributed.broadcast(group.kinematics.rotation_deviation_parameters.detach(), src=source)
-                if "translation_deviations" in self.parameters:
-                    torch.distributed.broadcast(group.kinematics.translation_deviation_parameters.detach(), src=source)
-                torch.distributed.broadcast(group.kinematics.actuators.optimizable_parameters.detach(), src=source)
-        torch.distributed.all_reduce(final_loss_per_heliostat, op=torch.distributed.ReduceOp.MIN)
-        histories: list = [[] for _ in range(ddp["world_size"])]
-        torch.distributed.all_gather_object(histories, loss_history)
-        log.info(f"Rank: {ddp['rank']}, synchronized after kinematics reconstruction.")
-        return histories
+        are learned - from the first rank that owns the group, the final losses MIN-reduced (a heliostat another rank
+        reconstructed is ``inf`` here), the histories of all ranks gathered (:650-705).  Returns the histories per rank;
+        ``[loss_history]`` in a single process."""
+        def tensors(group):
+            kinematics = group.kinematics
+            learned = [kinematics.translation_deviation_parameters] if "translation_deviations" in self.parameters else []
+            return [kinematics.rotation_deviation_parameters, *learned, kinematics.actuators.optimizable_parameters]
+        return self._gather(final_loss_per_heliostat, loss_history, tensors)
+
+    # ------------------------------------------------------------------------------------------ the loop's four places
+    def _before_optimizer_step(self, state: KinematicsGroupState, outcome: tuple, device) -> None:
+        if self._flux_driven:
+            self._synchronize_gradients_nested_ddp(state.optimizer)
+        else:
+            # a sample whose normals are parallel has a non-finite gradient: it does not take part in the epoch
+            for parameter in state.learnables.values():
+                parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
+
+    def _host_values(self, total: torch.Tensor) -> list:
+        return [total.item()]                       # the epoch's one read
 
     def reconstruct_kinematics(self, loss_definition, device: torch.device | None = None):
-        """Reconstruct the rotation deviations (or what ``self.parameters`` names) of the groups this rank owns (:707-884 alignment-driven, :886-1063
-        flux-driven).  Returns ``(final loss per heliostat of the scenario on the CPU, +inf where a heliostat was not
-        reconstructed; the histories: one list per rank, one entry per group)``; an entry is ``{"total_loss": a float per epoch,
-        "test_loss": the last validation's {"pixel_loss", "kl_div", "focal_spot_loss"} per heliostat}``.  A group runs while its
-        loss is above ``tolerance`` and ``epoch <= max_epoch``, or until early stopping, which ends the group before that
-        epoch's history entry.  The flux-driven mode averages the gradients over a group's sub-world and synchronises the
-        ranks afterwards; the alignment-driven mode issues no collective, as in the reference, and returns this rank's
-        histories alone.  The learned tensors are detached at the end."""
-        device = _gpu_device(device)
-        ddp = self.ddp_setup
-        rank = ddp["rank"]
-        if rank == 0:
+        """Reconstruct the rotation deviations (or what ``self.parameters`` names) of the groups this rank owns (:707-884
+        alignment-driven, :886-1063 flux-driven).  Returns ``(final loss per heliostat of the scenario on the CPU, +inf where a
+        heliostat was not reconstructed; the histories: one list per rank, one entry per group)``; an entry is ``{"total_loss":
+        a float per epoch, "test_loss": the last validation's {"pixel_loss", "kl_div", "focal_spot_loss"} per heliostat}``.  A
+        group runs while its loss is above ``tolerance`` and ``epoch <= max_epoch``, or until early stopping, which ends the
+        group before that epoch's history entry (``Reconstructor._reconstruct``).  The flux-driven mode averages the gradients
+        over a group's sub-world and synchronises the ranks afterwards; the alignment-driven mode issues no collective, as in
+        the reference, and returns this rank's histories alone.  The learned tensors are detached at the end."""
+        device = self._device(device)
+        if self.ddp_setup["rank"] == 0:
             log.info("Beginning kinematics reconstruction with %s.", "ray tracing" if self._flux_driven else "alignment")
-        groups = self.scenario.heliostat_field.heliostat_groups
-        sizes = [int(group.number_of_heliostats) for group in groups]
-        final_loss_per_heliostat = torch.full((sum(sizes),), torch.inf, device=device)
-        tolerance, max_epoch = float(self.optimizer_dict["tolerance"]), int(self.optimizer_dict["max_epoch"])
-        log_step = max_epoch if self.optimizer_dict["log_step"] == 0 else int(self.optimizer_dict["log_step"])
-        loss_history: list[dict] = []
-
-        for group_index in ddp["groups_to_ranks_mapping"][rank]:
-            state = self.prepare(group_index, device)
-            if state is None:                                        # a group without samples
-                continue
-            optimizer, scheduler = state.optimizer, state.scheduler
-            total_loss: list[float] = []
-            test_loss = None
-            loss_host = float("inf")
-            epoch = 0
-            graph = self.build_epoch_graph(state, loss_definition, device) if self.epoch_graph else None
-            try:
-                while loss_host > tolerance and epoch <= max_epoch:
-                    optimizer.zero_grad()
-                    if graph is None:
-                        loss = self.epoch_loss(state, loss_definition, device)
-                        loss.total.backward()
-                        total, per_heliostat = loss.total, loss.per_heliostat
-                    else:
-                        total, per_heliostat, _ = graph.replay()
-                    if self._flux_driven:
-                        self._synchronize_gradients_nested_ddp(optimizer)
-                    else:
-                        # a sample whose normals are parallel has a non-finite gradient: it does not take part in the epoch
-                        for parameter in state.learnables.values():
-                            parameter.grad.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
-                    optimizer.step()
-                    loss_host = total.item()                             # the epoch's one read, after the step has been queued
-                    if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
-                        scheduler.step(loss_host)
-                    else:
-                        scheduler.step()
-                    stop = state.early_stopper.step(loss_host)
-                    if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
-                        log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
-                        test_loss = self.validate(state, device)
-                    if stop:
-                        log.info(f"Early stopping at epoch {epoch}.")
-                        break
-                    total_loss.append(loss_host)
-                    epoch += 1
-                loss_history.append({"total_loss": total_loss, "test_loss": test_loss})
-
-                _, heliostat_rows = self._rank_rows(state, device)
-                rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
-                final_loss_per_heliostat[rows + sum(sizes[:group_index])] = per_heliostat.detach()          # (the last replay's)
-            finally:
-                if graph is not None:
-                    self.close_epoch_graph(state)
-            log.info(f"Rank: {rank}, Kinematics reconstructed.")
-
+        final_loss_per_heliostat, loss_history = self._reconstruct(loss_definition, device)
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history) if self._flux_driven \
             else [loss_history]
-        for group in groups:
+        for group in self.scenario.heliostat_field.heliostat_groups:
             for name in self.parameters:
                 holder, attribute, _ = _slot(group.kinematics, name)
                 setattr(holder, attribute, getattr(holder, attribute).detach())

@@ -44,11 +44,11 @@ from typing import Any
 
 import torch
 
-from . import _lib, distributed, training
-from ._memo import Memo
+from . import reconstruction
 from .flux import KLDivergenceLoss, PixelLoss, crop_flux_distributions_around_center
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid
 from .raytracing import HeliostatRayTracer
+from .reconstruction import LearnsParameters, ReconstructionGroupState, Reconstructor, _TakesParameters, tensors_held_by  # noqa: F401
 from .regularizers import surface_regularization_terms
 from .training import reduce_loss_per_sample
 
@@ -79,31 +79,18 @@ LEARNING_RATE_KEYS = {"nurbs_control_points": "initial_learning_rate", "canting"
 
 
 def canonical_parameters(parameters, names=PARAMETER_NAMES) -> tuple:
-    """``parameters`` - a non-empty tuple or list of ``names`` (a reconstructor's parameter names in their canonical order;
-    the surface reconstructor's by default), in any order, duplicates allowed - as a tuple in the canonical order.  Anything
-    else is a ``ValueError`` that lists the names."""
-    allowed = ", ".join(repr(name) for name in names)
-    if not isinstance(parameters, (tuple, list)) or len(parameters) == 0:
-        raise ValueError(f"parameters must be a non-empty tuple or list drawn from {allowed}; got {parameters!r}")
-    unknown = [name for name in parameters if name not in names]
-    if unknown:
-        raise ValueError(f"unknown parameter(s) {unknown!r}: parameters must be drawn from {allowed}")
-    return tuple(name for name in names if name in parameters)
+    """``reconstruction.canonical_parameters`` with the surface reconstructor's names as the default."""
+    return reconstruction.canonical_parameters(parameters, names)
 
 
 def learning_rates(optimizer_dict: dict, parameters=None, keys=LEARNING_RATE_KEYS) -> dict:
-    """The initial learning rate of every name in ``parameters`` (by default all of ``keys``; of the surface reconstructor's
-    own keys the three ``GEOMETRY_PARAMETER_NAMES``), in the canonical order, from
-    the configuration's ``"optimization"`` table.  ``keys`` maps a reconstructor's parameter names, in their canonical order,
-    to their configuration keys; the first key is required, the others are optional and default to it.  For the surface
-    reconstructor (the default): ``"initial_learning_rate"`` for the control points, ``"initial_learning_rate_canting"`` and
-    ``"initial_learning_rate_facet_translations"`` for the two rigid tensors, ``"initial_learning_rate_slope_errors"`` for sigma."""
-    names = tuple(keys)
+    """``reconstruction.learning_rates`` with the surface reconstructor's keys as the default: ``"initial_learning_rate"`` for
+    the control points, ``"initial_learning_rate_canting"`` and ``"initial_learning_rate_facet_translations"`` for the two
+    rigid tensors, ``"initial_learning_rate_slope_errors"`` for sigma.  Asked for no names in particular, these keys report
+    the three ``GEOMETRY_PARAMETER_NAMES``."""
     if parameters is None and keys is LEARNING_RATE_KEYS:
         parameters = GEOMETRY_PARAMETER_NAMES
-    default = float(optimizer_dict[keys[names[0]]])
-    return {name: float(optimizer_dict.get(keys[name], default))
-            for name in canonical_parameters(names if parameters is None else parameters, names)}
+    return reconstruction.learning_rates(optimizer_dict, parameters, keys)
 
 
 def flux_integral_constraint(cropped_sums: torch.Tensor, reference: torch.Tensor, multiplier, rho: float, energy_tolerance: float,
@@ -168,99 +155,28 @@ class EpochLoss:
                 (self.beta * self.ideal).mean(), self.relative_differences.mean(), self.constraint.mean())])
 
 
-@dataclass
-class GroupState:
-    """What the epochs of one heliostat group share (``SurfaceReconstructor.prepare``)."""
-    index: int
-    group: Any
-    mask: torch.Tensor
-    split: training.TrainTestSplit
-    active_rows: torch.Tensor                   # group-local rows of the heliostats that have samples, [active] on the device
-    original_control_points: torch.Tensor       # their nets before the first step (frozen), [active, F, U, V, 3]
+@dataclass(kw_only=True)
+class GroupState(ReconstructionGroupState):
+    """What the epochs of one heliostat group share (``SurfaceReconstructor.prepare``), beside the fields every reconstruction
+    has."""
+    original_control_points: torch.Tensor       # the active heliostats' nets before the first step (frozen), [active, F, U, V, 3]
     evaluation_points: torch.Tensor             # [active, F, M, 2] (expanded)
     canting: torch.Tensor
     facet_translations: torch.Tensor
-    optimizer: torch.optim.Optimizer
-    scheduler: Any
-    early_stopper: training.EarlyStopping
     multiplier: torch.Tensor                    # lambda of the flux-integral constraint, [this rank's heliostats]
     reference_integrals: torch.Tensor | None = None
-    activated: str | None = None                # "train" / "test": which samples the group is activated for
-    tracers: dict = field(default_factory=dict)
     aim_points: dict = field(default_factory=dict)
-    rows: dict = field(default_factory=dict)    # per kind: (sample rows, heliostat rows) of this rank, None = all
-    # this rank's rows of the per-sample tensors (_own): flux and targets, train and test - four, so eight are never reached
-    own: Memo = field(default_factory=lambda: Memo("this rank's rows of a per-sample tensor", capacity=8, under_capture="serve"))
-    # epoch_graph: the captured training step, whether the state a captured step reads must stay where it is, what is kept alive
-    # for the graph, and the ideal mount's orientations per kind (constants; their geometry copies from the host in every call)
-    graph: Any = None
+    # epoch_graph: whether the state a captured step reads must stay where it is, and the ideal mount's orientations per kind
+    # (constants; their geometry copies from the host in every call)
     static: bool = False
-    kept: list = field(default_factory=list)
     orientations: dict = field(default_factory=dict)
-    # what learns: name -> the group's own tensor, in the canonical order (PARAMETER_NAMES); and those among them that did not
-    # require grad before ``prepare`` marked them
-    learnables: dict = field(default_factory=dict)
+    # the learnables (in the order of PARAMETER_NAMES) that did not require grad before ``prepare`` marked them
     marked: list = field(default_factory=list)
     # a group with slope errors: zeta of the heliostats that have samples, [active, F, M, 2] (a constant of the run)
     slope_sample: torch.Tensor | None = None
 
 
-def tensors_held_by(*holders, depth: int = 3) -> list:
-    """Every tensor that ``holders`` - tensors, lists, tuples, dicts, objects with attributes - hold, ``depth`` levels down: what
-    a reconstructor keeps for as long as a captured step reads it (``torch.cuda.graph`` does not keep a capture's inputs)."""
-    found = []
-    for holder in holders:
-        if isinstance(holder, torch.Tensor):
-            found.append(holder)
-        elif depth > 0 and holder is not None:
-            inner = holder.values() if isinstance(holder, dict) else holder if isinstance(holder, (list, tuple)) else \
-                vars(holder).values() if hasattr(holder, "__dict__") else ()
-            found += tensors_held_by(*inner, depth=depth - 1)
-    return found
-
-
-def _gpu_device(device) -> torch.device:
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
-    device = torch.device("cpu") if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise _lib.ArtistHipError(f"SurfaceReconstructor runs on the GPU only (device {device}); there is no CPU fallback")
-    return device
-
-
-class _TakesParameters(type):
-    """``SurfaceReconstructor(..., epoch_graph=False, parameters=(...))``: the class call takes the one keyword that the
-    reference's constructor has no place for, checks it before ``__init__`` runs - so before any device work - and sets the
-    attribute.  ``__init__`` itself keeps the signature both reconstructors share, the reference's arguments and then
-    ``epoch_graph`` (tests/test_reconstructor_graphs_host.py holds it to that).  ``KinematicsReconstructor`` takes its
-    keyword the same way: the class's ``PARAMETER_NAMES`` are the names it draws from, the first of them the default."""
-
-    _first = object()       # (the keyword left out; None is a wrong value like any other)
-
-    def __call__(cls, *args, parameters=_first, **kwargs):
-        names = cls.PARAMETER_NAMES
-        chosen = canonical_parameters(names[:1] if parameters is _TakesParameters._first else parameters, names)
-        reconstructor = super().__call__(*args, **kwargs)
-        reconstructor.parameters = chosen
-        return reconstructor
-
-
-class LearnsParameters(metaclass=_TakesParameters):
-    """What the reconstructors share of the keyword: the attribute ``parameters``, checked and ordered on assignment against
-    the class's ``PARAMETER_NAMES``; the first name alone unless chosen otherwise."""
-    PARAMETER_NAMES: tuple = ()
-    _parameters = None
-
-    @property
-    def parameters(self) -> tuple:
-        """What learns, in the canonical order (``PARAMETER_NAMES``)."""
-        return type(self).PARAMETER_NAMES[:1] if self._parameters is None else self._parameters
-
-    @parameters.setter
-    def parameters(self, parameters) -> None:
-        self._parameters = canonical_parameters(parameters, type(self).PARAMETER_NAMES)
-
-
-class SurfaceReconstructor(LearnsParameters):
+class SurfaceReconstructor(Reconstructor):
     """``artist.optim.SurfaceReconstructor``: see the module docstring; attributes as in the reference (:58-84).
 
     ``prepare`` / ``predict_flux`` / ``epoch_loss`` / ``validate`` are the pieces ``reconstruct_surfaces`` runs per group, for
@@ -302,7 +218,7 @@ class SurfaceReconstructor(LearnsParameters):
                  plot_results: bool = False, device: torch.device | None = None, epoch_graph: bool = False) -> None:
         if plot_results:
             raise NotImplementedError("plot_results=True: plotting stays ARTIST's (artist/optim/surface_reconstructor.py)")
-        _gpu_device(device)
+        self._device(device)
         if ddp_setup["rank"] == 0:
             log.info("Create a surface reconstructor.")
         self.ddp_setup = ddp_setup
@@ -322,6 +238,8 @@ class SurfaceReconstructor(LearnsParameters):
         self.validation_loss_kl_div = KLDivergenceLoss()
 
     PARAMETER_NAMES = PARAMETER_NAMES           # (the control points alone, unless chosen otherwise)
+    HISTORY_KEYS = HISTORY_KEYS
+    RECONSTRUCTS = "surface"
 
     # ------------------------------------------------------------------------------------------
     def prepare(self, heliostat_group_index: int, device: torch.device | None = None) -> GroupState | None:
@@ -330,36 +248,23 @@ class SurfaceReconstructor(LearnsParameters):
         nets of the heliostats that have samples, ``artist_amd.optim.Adam`` with one parameter group per tensor of
         ``self.parameters`` (``requires_grad_()`` on those, and on no other), the configured scheduler, early stopping and a
         zero multiplier.  None for a group without samples."""
-        from .optim import Adam
         group = self.scenario.heliostat_field.heliostat_groups[heliostat_group_index]
         if "slope_errors" in self.parameters and getattr(group, "slope_errors", None) is None:
             raise ValueError(f"parameters={self.parameters!r}: heliostat group {heliostat_group_index} has no slope_errors to start "
                              "from; set group.slope_errors to a tensor with one sigma per heliostat before the reconstruction")
-        device = _gpu_device(device)
-        flux_measured, focal_spots, incident, motor_positions, mask, targets = self.data["data_parser"].parse_data_for_reconstruction(
-            heliostat_data_mapping=self.data["heliostat_data_mapping"], heliostat_group=group, scenario=self.scenario,
-            bitmap_resolution=self.bitmap_resolution, device=device)
-        active_rows = torch.nonzero(mask > 0, as_tuple=True)[0]
-        if active_rows.numel() == 0:
+        device = self._device(device)
+        parsed = self._parse_and_split(heliostat_group_index, device)
+        if parsed is None:
             return None
-        split = training.train_test_split(active_heliostats_mask=mask, flux_measured=flux_measured, focal_spots_measured=focal_spots,
-                                          incident_ray_directions=incident, motor_positions=motor_positions,
-                                          target_area_indices=targets, device=device)
+        (_, _, _, _, mask, _), split, active_rows = parsed
         active = int(active_rows.numel())
         grid = create_nurbs_evaluation_grid(self.number_of_surface_points, device=device)
         with torch.no_grad():
             original = group.nurbs_control_points.index_select(0, active_rows).clone()
-        # the leaves are only marked here: nothing builds an autograd graph through them before the first step (graphs.py,
-        # "Fresh leaves"); a tensor that is not chosen is left as it is
-        rates = learning_rates(self.optimizer_dict, self.parameters)
+        # a tensor that is not chosen is left as it is
         learnables = {name: getattr(group, name) for name in self.parameters}
         marked = [tensor for name, tensor in learnables.items() if name != "nurbs_control_points" and not tensor.requires_grad]
-        optimizer = Adam([dict(params=[tensor.requires_grad_()], lr=rates[name]) for name, tensor in learnables.items()],
-                         lr=float(self.optimizer_dict["initial_learning_rate"]))
-        scheduler = getattr(training, self.scheduler_dict["scheduler_type"])(optimizer=optimizer, parameters=self.scheduler_dict)
-        stopper = training.EarlyStopping(window_size=self.optimizer_dict["early_stopping_window"],
-                                         patience=self.optimizer_dict["early_stopping_patience"],
-                                         min_improvement=self.optimizer_dict["early_stopping_delta"], relative=True)
+        optimizer, scheduler, stopper = self._optimizer_for(learnables, LEARNING_RATE_KEYS)
         state = GroupState(index=heliostat_group_index, group=group, mask=mask, split=split, active_rows=active_rows,
                            original_control_points=original,
                            evaluation_points=grid[None, None].expand(active, int(group.number_of_facets_per_heliostat), -1, -1),
@@ -374,24 +279,6 @@ class SurfaceReconstructor(LearnsParameters):
         _, heliostat_rows = self._rank_rows(state, "train", device)
         state.multiplier = torch.zeros(active if heliostat_rows is None else int(heliostat_rows.numel()), device=device)
         return state
-
-    def _rank_rows(self, state: GroupState, kind: str, device):
-        """``(sample rows, heliostat rows)`` that this rank owns among the group's samples of ``kind`` and among its active
-        heliostats - index tensors on the device, or ``(None, None)`` when it owns all.  From the sampler's host list
-        (artist/raytracing/sampling.py:107-157): a heliostat's samples stay together."""
-        if kind not in state.rows:
-            split = state.split
-            samples = split.number_of_train_samples if kind == "train" else split.number_of_test_samples
-            active = int(state.active_rows.numel())
-            from .sampling import RestrictedDistributedSampler
-            owned = RestrictedDistributedSampler(active * samples, active, self.ddp_setup["heliostat_group_world_size"],
-                                                 self.ddp_setup["heliostat_group_rank"]).rank_indices
-            if owned == list(range(active * samples)):
-                state.rows[kind] = (None, None)
-            else:
-                state.rows[kind] = (torch.tensor(owned, dtype=torch.long, device=device),
-                                    torch.tensor([i // samples for i in owned[::samples]], dtype=torch.long, device=device))
-        return state.rows[kind]
 
     def _cropped_flux(self, state: GroupState, kind: str, device) -> torch.Tensor:
         """Control points -> cropped flux of this rank's samples of ``kind`` (:476-591 and :197-262): evaluate each active
@@ -456,18 +343,10 @@ class SurfaceReconstructor(LearnsParameters):
         return crop_flux_distributions_around_center(flux_distributions=flux, solar_tower=tower,
                                                      target_area_indices=self._own(state, kind, targets, device), device=device)
 
-    def _own(self, state: GroupState, kind: str, per_sample: torch.Tensor, device) -> torch.Tensor:
-        """This rank's rows of a per-sample tensor of ``kind``; the tensor itself when the rank owns all (kept per tensor object
-        and version, so that callers which remember a tensor object they have checked meet the same object every epoch)."""
-        sample_rows, _ = self._rank_rows(state, kind, device)
-        if sample_rows is None:
-            return per_sample
-        return state.own.lookup(per_sample, lambda: per_sample.index_select(0, sample_rows), key=kind)
-
     def predict_flux(self, state: GroupState, device: torch.device | None = None) -> torch.Tensor:
         """The cropped flux of this rank's training samples from the group's current control points,
         ``[samples, res_u, res_e]``, inside the autograd graph (:476-591)."""
-        return self._cropped_flux(state, "train", _gpu_device(device))
+        return self._cropped_flux(state, "train", self._device(device))
 
     def epoch_loss(self, state: GroupState, cropped_flux: torch.Tensor, loss_definition,
                    device: torch.device | None = None) -> EpochLoss:
@@ -475,7 +354,7 @@ class SurfaceReconstructor(LearnsParameters):
         the mean per heliostat, :func:`flux_integral_constraint` - the first call's cropped sums become the reference
         integrals (``state.reference_integrals`` is None before) - and ``alpha S + beta I`` with the dynamic balancing of
         ``artist_amd.surface_regularization_terms``.  The multiplier is left as it is: :meth:`update_multiplier`."""
-        device = _gpu_device(device)
+        device = self._device(device)
         split = state.split
         samples = split.number_of_train_samples
         per_sample = loss_definition(prediction=cropped_flux, ground_truth=self._own(state, "train", split.flux_measured_train, device),
@@ -514,7 +393,7 @@ class SurfaceReconstructor(LearnsParameters):
         """The group's test samples under the current control points (:157-303), without gradient: ``{"pixel_loss", "kl_div"}``,
         each the mean over a heliostat's test samples, ``[this rank's heliostats]`` on the device.  Leaves the group activated
         for the test samples; the next ``predict_flux`` activates it for training again."""
-        device = _gpu_device(device)
+        device = self._device(device)
         split = state.split
         with torch.no_grad():
             cropped = self._cropped_flux(state, "test", device)
@@ -541,42 +420,28 @@ class SurfaceReconstructor(LearnsParameters):
         tables, which ``activate_heliostats`` rebinds and never writes, the reference integrals, the aim points, the rank's
         rows), so that a validation is not handed their memory.  The step is not activated for training again after a
         validation.  :meth:`close_epoch_graph` ends it."""
-        from . import graphs
-        device = _gpu_device(device)
+        device = self._device(device)
         state.static = True
+        return self._capture(state, loss_definition, device)
 
-        def step():
-            loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
-            loss.total.backward()
-            return loss.scalars(), loss.total_per_heliostat.detach(), loss.flux_loss_per_sample.detach(), loss.violation.detach()
-
-        try:
-            state.graph = graphs.EpochGraph(step, warmup=2, parameters=list(state.learnables.values()), device=device)
-        except BaseException:
-            self.close_epoch_graph(state)
-            raise
-        kinematics = getattr(state.group, "kinematics", None)
-        state.kept = tensors_held_by(state, state.group, kinematics, getattr(kinematics, "actuators", None))
-        return state.graph
+    def _step(self, state: GroupState, loss_definition, device) -> tuple:
+        """``(the six history scalars [6], total loss per heliostat, flux loss per sample, violation)``, detached."""
+        loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
+        loss.total.backward()
+        return loss.scalars(), loss.total_per_heliostat.detach(), loss.flux_loss_per_sample.detach(), loss.violation.detach()
 
     def close_epoch_graph(self, state: GroupState) -> None:
         """Close ``state.graph`` and let go of what was kept for it.  No autograd graph that was built on the graph's stream
         outlives it: the surfaces the capture left on the group are detached."""
-        if state.graph is not None:
-            state.graph.close()
-        state.graph, state.static, state.kept = None, False, []
-        group = state.group
-        group.active_surface_points, group.active_surface_normals = group.active_surface_points.detach(), group.active_surface_normals.detach()
+        state.static = False
+        self._release(state)
 
     def _synchronize_and_lock_gradients(self, parameter: torch.Tensor, device: torch.device | None = None) -> None:
         """In nested mode the ranks that share a group average the gradient: SUM over ``process_subgroup``, divided by the
         sub-world size.  Then the outer edges are locked (:749-788)."""
         if parameter.grad is None:
             return
-        ddp = self.ddp_setup
-        if ddp["is_nested"]:
-            distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
-            parameter.grad /= ddp["heliostat_group_world_size"]
+        self._nested_mean(parameter.grad)
         parameter.grad = self.lock_control_points_on_outer_edges(gradients=parameter.grad, device=device)
 
     def _synchronize_and_zero_w_gradients(self, parameter: torch.Tensor, device: torch.device | None = None) -> None:
@@ -587,19 +452,13 @@ class SurfaceReconstructor(LearnsParameters):
         points' w away from 1."""
         if parameter.grad is None:
             return
-        ddp = self.ddp_setup
-        if ddp["is_nested"]:
-            distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
-            parameter.grad /= ddp["heliostat_group_world_size"]
+        self._nested_mean(parameter.grad)
         with torch.no_grad():
             parameter.grad[..., 3] = 0
 
     def _synchronize_gradients(self, parameter: torch.Tensor) -> None:
         """The nested average alone, for ``slope_errors`` ``[N]``: every component is a parameter."""
-        ddp = self.ddp_setup
-        if parameter.grad is not None and ddp["is_nested"]:
-            distributed.all_reduce_sum(parameter.grad, group=ddp["process_subgroup"])
-            parameter.grad /= ddp["heliostat_group_world_size"]
+        self._nested_mean(parameter.grad)
 
     def _synchronize_and_lock_learnables(self, state: GroupState, device: torch.device | None = None) -> None:
         """Before the step: one reduce per learnable tensor in the canonical order (the same on every rank), the edge lock on
@@ -614,97 +473,37 @@ class SurfaceReconstructor(LearnsParameters):
 
     def _synchronize_reconstruction_across_ranks(self, final_loss_per_heliostat: torch.Tensor, loss_history: list) -> list:
         """Every group's learnable tensors (the control points by default) from the first rank that owns the group, the
-        final losses MIN-reduced (a heliostat
-        another rank reconstructed is ``inf`` here), the histories of all ranks gathered (:790-840).  Returns the histories
-        per rank; ``[loss_history]`` in a single process."""
-        ddp = self.ddp_setup
-        if not ddp["is_distributed"]:
-            return [loss_history]
-        with torch.no_grad():
-            for index, group in enumerate(self.scenario.heliostat_field.heliostat_groups):
-                for name in self.parameters:
-                    torch.distributed.broadcast(getattr(group, name).detach(), src=ddp["ranks_to_groups_mapping"][index][0])
-        torch.distributed.all_reduce(final_loss_per_heliostat, op=torch.distributed.ReduceOp.MIN)
-        histories: list = [[] for _ in range(ddp["world_size"])]
-        torch.distributed.all_gather_object(histories, loss_history)
-        log.info(f"Rank: {ddp['rank']}, synchronized after surface reconstruction.")
-        return histories
+        final losses MIN-reduced (a heliostat another rank reconstructed is ``inf`` here), the histories of all ranks
+        gathered (:790-840).  Returns the histories per rank; ``[loss_history]`` in a single process."""
+        return self._gather(final_loss_per_heliostat, loss_history, lambda group: [getattr(group, name) for name in self.parameters])
+
+    # ------------------------------------------------------------------------------------------ the loop's four places
+    def _before_optimizer_step(self, state: GroupState, outcome: tuple, device) -> None:
+        self.update_multiplier(state, outcome[3])   # (the violation)
+        self._synchronize_and_lock_learnables(state, device)
+
+    def _host_values(self, scalars: torch.Tensor) -> list:
+        return scalars.tolist()                     # the epoch's six scalars in ONE transfer
+
+    def _finish_group(self, state: GroupState) -> None:
+        for tensor in state.marked:                 # the rigid tensors are constants again for whoever evaluates next
+            tensor.requires_grad_(False)
+        if "slope_errors" in state.learnables:      # zeta is symmetric: a learnt sigma is reported as its magnitude
+            with torch.no_grad():
+                state.learnables["slope_errors"].abs_()
 
     def reconstruct_surfaces(self, loss_definition, device: torch.device | None = None):
         """Reconstruct the surfaces of the groups this rank owns (:842-1160).  Returns ``(final loss per heliostat of the
         scenario on the CPU, +inf where a heliostat was not reconstructed; the histories: one list per rank, one entry per
         group)``; an entry has the per-epoch float lists ``HISTORY_KEYS`` and ``"test_loss"``, the last validation's
         ``{"pixel_loss", "kl_div"}`` per heliostat.  A group runs while its loss is above ``tolerance`` and
-        ``epoch <= max_epoch``, or until early stopping, which ends the group before that epoch's history entry.  Afterwards
-        the ranks are synchronised and the field's surface points follow the new control points, canting and translations
-        (``update_surfaces``)."""
-        device = _gpu_device(device)
-        ddp = self.ddp_setup
-        rank = ddp["rank"]
-        if rank == 0:
+        ``epoch <= max_epoch``, or until early stopping, which ends the group before that epoch's history entry
+        (``Reconstructor._reconstruct``).  Afterwards the ranks are synchronised and the field's surface points follow the new
+        control points, canting and translations (``update_surfaces``)."""
+        device = self._device(device)
+        if self.ddp_setup["rank"] == 0:
             log.info("Beginning surface reconstruction.")
-        groups = self.scenario.heliostat_field.heliostat_groups
-        sizes = [int(group.number_of_heliostats) for group in groups]
-        final_loss_per_heliostat = torch.full((sum(sizes),), torch.inf, device=device)
-        tolerance, max_epoch = float(self.optimizer_dict["tolerance"]), int(self.optimizer_dict["max_epoch"])
-        log_step = max_epoch if self.optimizer_dict["log_step"] == 0 else int(self.optimizer_dict["log_step"])
-        loss_history: list[dict] = []
-
-        for group_index in ddp["groups_to_ranks_mapping"][rank]:
-            state = self.prepare(group_index, device)
-            if state is None:                                        # a group without samples
-                continue
-            optimizer, scheduler = state.optimizer, state.scheduler
-            history: dict = {key: [] for key in HISTORY_KEYS}
-            test_loss = None
-            loss_host = float("inf")
-            epoch = 0
-            graph = self.build_epoch_graph(state, loss_definition, device) if self.epoch_graph else None
-            try:
-                while loss_host > tolerance and epoch <= max_epoch:
-                    optimizer.zero_grad()
-                    if graph is None:
-                        loss = self.epoch_loss(state, self.predict_flux(state, device), loss_definition, device)
-                        loss.total.backward()
-                        violation, total_per_heliostat = loss.violation, loss.total_per_heliostat
-                    else:
-                        scalars_on_device, total_per_heliostat, _, violation = graph.replay()
-                    self.update_multiplier(state, violation)
-                    self._synchronize_and_lock_learnables(state, device)
-                    optimizer.step()
-                    # the epoch's scalars in ONE transfer, after the step has been queued
-                    scalars = (loss.scalars() if graph is None else scalars_on_device).tolist()
-                    loss_host = scalars[0]
-                    if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
-                        scheduler.step(loss_host)
-                    else:
-                        scheduler.step()
-                    stop = state.early_stopper.step(loss_host)
-                    if not log_step or epoch % log_step == 0 or epoch == max_epoch - 1 or stop:
-                        log.info(f"Rank: {rank}, Epoch: {epoch}, Loss: {loss_host}")
-                        test_loss = self.validate(state, device)
-                    if stop:
-                        log.info(f"Early stopping at epoch {epoch}.")
-                        break
-                    for key, value in zip(HISTORY_KEYS, scalars):
-                        history[key].append(value)
-                    epoch += 1
-                history["test_loss"] = test_loss
-                loss_history.append(history)
-
-                _, heliostat_rows = self._rank_rows(state, "train", device)
-                rows = state.active_rows if heliostat_rows is None else state.active_rows.index_select(0, heliostat_rows)
-                final_loss_per_heliostat[rows + sum(sizes[:group_index])] = total_per_heliostat.detach()    # (the last replay's)
-            finally:
-                if graph is not None:
-                    self.close_epoch_graph(state)
-                for tensor in state.marked:             # the rigid tensors are constants again for whoever evaluates next
-                    tensor.requires_grad_(False)
-                if "slope_errors" in state.learnables:  # zeta is symmetric: a learnt sigma is reported as its magnitude
-                    with torch.no_grad():
-                        state.learnables["slope_errors"].abs_()
-            log.info(f"Rank: {rank}, Surfaces reconstructed.")
-
+        final_loss_per_heliostat, loss_history = self._reconstruct(loss_definition, device)
         histories = self._synchronize_reconstruction_across_ranks(final_loss_per_heliostat, loss_history)
         self.scenario.heliostat_field.update_surfaces(device=device)
         return final_loss_per_heliostat.detach().cpu(), histories

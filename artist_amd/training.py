@@ -13,7 +13,7 @@ from typing import Any, Callable
 
 import torch
 
-__all__ = ["exponential", "cyclic", "reduce_on_plateau", "EarlyStopping", "TrainTestSplit", "train_test_split",
+__all__ = ["exponential", "cyclic", "reduce_on_plateau", "step_scheduler", "EarlyStopping", "TrainTestSplit", "train_test_split",
            "reduce_loss_per_sample"]
 
 
@@ -34,6 +34,14 @@ def reduce_on_plateau(optimizer: torch.optim.Optimizer, parameters: dict) -> tor
     return torch.optim.lr_scheduler.ReduceLROnPlateau(
         optimizer, factor=float(parameters["reduce_factor"]), patience=int(parameters["patience"]),
         threshold=float(parameters["threshold"]), cooldown=int(parameters["cooldown"]), min_lr=float(parameters["lr_min"]))
+
+
+def step_scheduler(scheduler, loss: float) -> None:
+    """One epoch's step of ``scheduler``: ``ReduceLROnPlateau`` wants the epoch's loss, the others take nothing."""
+    if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+        scheduler.step(loss)
+    else:
+        scheduler.step()
 
 
 class EarlyStopping:

@@ -37,8 +37,11 @@ def test_the_names_are_exported():
     assert optim.KinematicsReconstructor.PARAMETER_NAMES == NAMES
     assert tuple(kinematics_reconstructor.KINEMATICS_LEARNING_RATE_KEYS) == NAMES
     assert tuple(kinematics_reconstructor.KINEMATICS_LEARNING_RATE_KEYS.values()) == RATE_KEYS
-    # one helper for both reconstructors
-    assert kinematics_reconstructor.learning_rates is surface_reconstructor.learning_rates
+    # one helper for both reconstructors: the rates are read where the optimiser is built, in the base both classes share
+    from artist_amd import reconstruction
+    assert optim.KinematicsReconstructor._optimizer_for is optim.SurfaceReconstructor._optimizer_for is reconstruction.Reconstructor._optimizer_for
+    assert surface_reconstructor.learning_rates({RATE_KEYS[0]: 2e-4}, NAMES[:1], kinematics_reconstructor.KINEMATICS_LEARNING_RATE_KEYS) == \
+        reconstruction.learning_rates({RATE_KEYS[0]: 2e-4}, NAMES[:1], kinematics_reconstructor.KINEMATICS_LEARNING_RATE_KEYS) == {NAMES[0]: 2e-4}
     assert issubclass(optim.KinematicsReconstructor, surface_reconstructor.LearnsParameters)
     assert issubclass(optim.SurfaceReconstructor, surface_reconstructor.LearnsParameters)
 

@@ -91,8 +91,8 @@ def _worker(rank, world, port, out_dir):
             for name in ("all_reduce", "broadcast", "all_gather_object"):
                 setattr(dist, name, lambda *a, _name=name, **k: calls.append(_name))
             # (in this process only: the bookkeeping of a run without groups on CPU tensors - there is no GPU here)
-            from artist_amd import kinematics_reconstructor
-            kinematics_reconstructor._gpu_device = lambda device: torch.device("cpu")
+            from artist_amd import reconstruction
+            reconstruction.gpu_device = lambda device, who: torch.device("cpu")
             final_loss, histories = _reconstructor(no_groups, scenario, "alignment").reconstruct_kinematics(None, torch.device("cuda", 0))
             assert calls == [] and histories == [[]] and final_loss.tolist() == [float("inf")] * 2
             assert not groups[0].kinematics.rotation_deviation_parameters.requires_grad          # detached at the end
