@@ -86,9 +86,27 @@ def plateau_hyperparameters(scheduler) -> dict | None:
                 cooldown_counter=int(scheduler.cooldown_counter))
 
 
+def _net_block_error(nu: int, nv: int, p: int, q: int, epochs: int):
+    """``on_error`` of the loop kernels' calls.  The number of points is no limit (beyond 2^20 rows per facet, which is
+    ``ART_EINVAL``): a facet whose per-point arrays do not fit in LDS is evaluated in chunks.  What has to fit in a CU's 160 KiB
+    is the net's own block, and ``ART_EUNSUPPORTED`` says that it does not."""
+    def on_error(code: int, name: str) -> None:
+        if code != _lib.ART_EUNSUPPORTED:
+            return _lib.check(code, name)
+        ncells, pq = (nu - p) * (nv - q), (p + 1) * (q + 1)
+        parts = {"control net and two Adam moments": 9 * nu * nv, "cell partial sums": 3 * ncells * pq,
+                 "bias-correction tables": 3 * epochs, "cell offsets": ncells + 3}
+        text = ", ".join(f"{k} {4 * v / 1024:.1f} KiB" for k, v in parts.items())
+        raise _lib.ArtistHipError(
+            f"{name}: the LDS block of a {nu} x {nv} net of degrees ({p}, {q}) does not fit in 160 KiB beside one chunk of 64 "
+            f"points ({text}; the number of points per facet does not enter: they are streamed in chunks). "
+            f"Use a smaller net{' or fewer epochs per launch' if epochs else ''}. (code {code})")
+    return on_error
+
+
 class _Prepared:
     """Buffers of ``art_surface_fit_prepare`` for a batch: what the loop kernels read, plus the evaluation points and the
-    initial nets."""
+    initial nets.  Any ``N`` up to 2^20 rows per facet; nothing but these buffers is sized by it."""
 
     def __init__(self, points: torch.Tensor, n_valid, nu: int, nv: int, p: int, q: int, knots_u, knots_v):
         dev = _require_cuda(points)
@@ -127,7 +145,8 @@ class _Prepared:
         nrm = torch.zeros_like(pts) if with_points else None
         _timed_call("art_surface_fit_loss_grad", self.device, cp.data_ptr(), targets.data_ptr(), self._nv_ptr(), self.perm.data_ptr(),
                     self.cell_start.data_ptr(), self.table.data_ptr(), self.B, self.N, self.nu, self.nv, self.p, self.q, method,
-                    loss.data_ptr(), grad.data_ptr(), None if pts is None else pts.data_ptr(), None if nrm is None else nrm.data_ptr())
+                    loss.data_ptr(), grad.data_ptr(), None if pts is None else pts.data_ptr(), None if nrm is None else nrm.data_ptr(),
+                    on_error=_net_block_error(self.nu, self.nv, self.p, self.q, 0))
         return (loss, grad, pts, nrm) if with_points else (loss, grad)
 
 
@@ -171,7 +190,7 @@ def run_epochs(prep: _Prepared, state: _FitState, targets: torch.Tensor, method:
                     chunk, float(tolerance), int(max_epoch), adam["betas"][0], adam["betas"][1], adam["eps"], adam["weight_decay"],
                     1 if adam["maximize"] else 0, 1 if sched["use"] else 0, 1 if sched["mode_max"] else 0, sched["factor"],
                     sched["patience"], sched["threshold"], 1 if sched["threshold_abs"] else 0, sched["cooldown"], sched["min_lr"],
-                    sched["eps"])
+                    sched["eps"], on_error=_net_block_error(prep.nu, prep.nv, prep.p, prep.q, chunk))
         epochs -= chunk
 
 
@@ -324,7 +343,9 @@ class SurfaceGenerator:
         """Fitted control points per facet (surface_generator.py:225-376): the facets' point and normal lists are truncated to
         the shortest facet, strided by ``deflectometry_step_size``, converted to 4D and fitted; the facet translation is added
         to the fitted net (zero translations for the point-cloud method, which learns them).  Returns a list of
-        :class:`FittedFacet` - plain data in place of the reference's ``SurfaceConfig``.
+        :class:`FittedFacet` - plain data in place of the reference's ``SurfaceConfig``.  The default stride of 100 is the
+        reference's (an eager fit is slow); here ``deflectometry_step_size=1`` - every measured point, up to 2^20 per facet -
+        is one launch like any other, with the same ordered sums (cost: DESIGN.md 4.7).
 
         Scheduler state: the reference passes one scheduler object to every facet's fit in turn, so ``best`` /
         ``num_bad_epochs`` of a ``ReduceLROnPlateau`` carry over from one facet into the next.  Here, by default

@@ -6,14 +6,24 @@
  *
  * Sizes: B facets, N rows of measured data per facet of which the first n_valid[b] count, a control net nu x nv of degrees
  * p, q (1..7, nu > p, nv > q) on clamped uniform knots.  ncells = (nu - p) * (nv - q) knot-span cells.
- * Limits: 1 <= N <= 16384, ncells <= 4096; everything a workgroup keeps in LDS (net, Adam moments, per-point gradients, cell
- * partial sums) must fit in 160 KiB, otherwise ART_EUNSUPPORTED - nothing falls back silently.  The per-point tables are
- * staged in LDS when they fit as well and are streamed from `table` otherwise: same arithmetic, same bits.
+ * Limits: 1 <= N <= 1048576 (2^20; more is ART_EINVAL, never narrowed), ncells <= 4096.  The number of points is otherwise
+ * no limit.  ART_EUNSUPPORTED is left for one case: the block of LDS that a workgroup keeps whatever N is - net, two Adam
+ * moments, cell partial sums, cell offsets, the launch's bias-correction tables: 3 epochs + 9 nu nv + 3 ncells (p+1)(q+1) +
+ * ncells + 3 floats - does not fit in 160 KiB beside 64 points.  Nothing falls back silently.
+ * LDS: when a facet's per-point arrays (gradient and squared error of every point: 7 N floats) fit beside that block - for a
+ * 10 x 10 degree-3 net and a 401-epoch launch up to N = 5207 - they stay resident for the whole launch, and the per-point
+ * tables are staged in LDS as well when they fit too (streamed from `table` otherwise).  Beyond that the points are taken in
+ * chunks of C sorted positions, C a multiple of 64 sized from what the block leaves (5184 in that example), table and
+ * targets streamed; prepare likewise sorts in tiles of 16384 rows when 2 N ints do not fit (or N > 16384).  Every sum keeps
+ * the owner and the order described below in every case - the running sum of a cell's control point and a lane's share of
+ * the loss are carried from chunk to chunk - so all of these paths give the same bits.
  *
  * Determinism: no float atomics anywhere.  Points are grouped by span cell; a cell's (p+1)(q+1) control points receive the
  * cell's points in index order, a control point then adds its at most (p+1)(q+1) cell sums in cell order, and the loss adds
  * the points in sorted order with lane l of one wave owning positions l, l + 64, ... in fp64 followed by a fixed shuffle tree.
- * A facet's bits depend on that facet's data alone: not on B, not on the neighbours, not on how epochs are chunked.
+ * A facet's bits depend on that facet's data alone: not on B, not on the padded row count N of its batch, not on the
+ * neighbours, not on how epochs are chunked into launches - although N and the epochs of a launch decide whether a facet is
+ * resident or taken in chunks, and how long a chunk is.
  */
 #ifndef ARTIST_HIP_SURFACE_FIT_H
 #define ARTIST_HIP_SURFACE_FIT_H

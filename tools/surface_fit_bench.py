@@ -10,7 +10,10 @@ Wall time per complete fit between device synchronisations (a fit is tens to tho
 of what is measured), two warm-up fits first, median / min / max and the relative spread over the repetitions; and how far the
 two results are apart.
 
-usage: python tools/surface_fit_bench.py [--reps 9 --loop-reps 5 --warmup 2 --sizes 4,400,4000] [--out FILE]
+With --points N the facets have N points each instead of 800 - above about 5000 `fit_nurbs_batch` evaluates a facet in chunks
+ -; profiles/surface_fit_bench_large.json holds such runs, one entry per (N, B).
+
+usage: python tools/surface_fit_bench.py [--reps 9 --loop-reps 5 --warmup 2 --sizes 4,400,4000] [--points N] [--out FILE]
 """
 import argparse
 import json
@@ -39,18 +42,25 @@ def wall_ms(fn, reps, warmup=1):
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3)
     ms.sort()
-    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1], "reps": reps,
+    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1], "reps": reps, "warmup": warmup,
             "spread_rel": (ms[-1] - ms[0]) / ms[len(ms) // 2]}
 
 
 def main():
+    global N
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--loop-reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--sizes", default="4,400,4000")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "surface_fit_bench.json"))
+    ap.add_argument("--points", type=int, default=N, help="points per facet (default 800)")
+    ap.add_argument("--out", default=None, help="default: profiles/surface_fit_bench.json, or, with --points, "
+                                                "profiles/surface_fit_bench_large.json, which gathers its runs under 'points'")
     args = ap.parse_args()
+    large = args.points != N
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("surface_fit_bench_large.json" if large else "surface_fit_bench.json"))
+    N = args.points
     if not torch.cuda.is_available():
         raise SystemExit("surface_fit_bench needs a GPU")
     import surface_fit_ref as sfr
@@ -97,7 +107,11 @@ def main():
               f"({entry['speedup_median']:.1f}x), max |cp difference| {diff:.2e}", flush=True)
         out_path = pathlib.Path(args.out)
         out_path.parent.mkdir(parents=True, exist_ok=True)
-        out_path.write_text(json.dumps(result, indent=1) + "\n")
+        doc = result
+        if large:       # one file for all point counts: this run's entry beside the ones already there
+            doc = json.loads(out_path.read_text()) if out_path.exists() else {"points": {}}
+            doc["points"].setdefault(str(N), result)["sizes"].update(result["sizes"])
+        out_path.write_text(json.dumps(doc, indent=1) + "\n")
     print(f"wrote {args.out}")
 
 
