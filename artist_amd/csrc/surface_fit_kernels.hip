@@ -19,9 +19,10 @@
 // B, not on the workgroup size (chosen from N), not on where the table lives (LDS when it fits, global otherwise), not on how
 // the epochs are chunked into launches.
 //
-// A facet with more points than LDS holds beside its net (a measured facet has ~80 000) is still one workgroup's: phases 1 and 2
-// then run per chunk of sorted positions with the running sums carried from chunk to chunk (fit_epoch_chunked), and prepare
-// sorts in tiles (surface_fit_prepare_tiled_kernel).  The order of every sum is the resident one, so are the bits.
+// A facet with more points than LDS holds beside its net (a measured facet has ~80 000) is still one workgroup's: the same
+// fit_epoch then runs phases 1 and 2 per chunk of sorted positions with the running sums carried from chunk to chunk (FitMode),
+// and prepare sorts in tiles (surface_fit_prepare_tiled_kernel).  There is one text of every expression of the fit, so the
+// order of every sum, and with it the bits, cannot differ between the two.
 // ARTIST_HIP_DEBUG=1 ARTIST_HIP_FIT_CHUNK=<points> forces both at any N with that chunk / tile length (tests).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -147,102 +148,26 @@ __device__ __forceinline__ double fit_wave_sum_f64(double v)
     return v;
 }
 
-// ---- the phases of fit_epoch (below) restated as functions for fit_epoch_chunked: the same expressions, so the same roundings.
-// fit_epoch itself and the resident kernels stay as they were written - their device code is, instruction for instruction, what
-// it was before the chunked path existed (routing them through these functions moved B = 4000 at N = 800 by 0.4 %, outside
-// the 0.2 % spread of the measurement: DESIGN.md 4.7).
-//
-// Phase 1 for one point: S, dS/du, dS/dv from its table row `rec` and the net, the squared error against target t to *sq and the
-// gradient w.r.t. S (points fit) or dS/du, dS/dv (normals fit) to go[0..ng); *row is the point's row in the caller's order.
-template <int DEG>
-__device__ __forceinline__ void fit_point(const FitArgs& a, const float* s_cp, const float* rec, const float4 t, const float scale,
-                                          const int b, const int32_t* row, float* go, float* sq)
-{
-    const bool fit_points = a.method == ART_FIT_POINTS;
-    float S0[4], Su[3], Sv[3];
-    fit_eval_point<DEG>(a, s_cp, rec, S0, Su, Sv);
-    // surfaces.py:615-661 (finish_point of nurbs_kernels.hip without canting)
-    const float cx = Su[1] * Sv[2] - Su[2] * Sv[1];
-    const float cy = Su[2] * Sv[0] - Su[0] * Sv[2];
-    const float cz = Su[0] * Sv[1] - Su[1] * Sv[0];
-    const float px = S0[0] / S0[3], py = S0[1] / S0[3], pz = S0[2] / S0[3];
-    const float ncl = fmaxf(norm3(cx, cy, cz), 1e-12f);
-    const float nx = cx / ncl, ny = cy / ncl, nz = cz / ncl;
-    float e0, e1, e2, e3;
-    if (fit_points) { e0 = px - t.x; e1 = py - t.y; e2 = pz - t.z; e3 = 1.0f - t.w; }
-    else { e0 = nx - t.x; e1 = ny - t.y; e2 = nz - t.z; e3 = 0.0f - t.w; }
-    *sq = ((e0 * e0 + e1 * e1) + e2 * e2) + e3 * e3;
-    const float g0 = scale * e0, g1 = scale * e1, g2 = scale * e2;
-    if (fit_points) {
-        const float iw = 1.0f / S0[3];
-        go[0] = g0 * iw; go[1] = g1 * iw; go[2] = g2 * iw;
-    } else {
-        // point_adjoint of nurbs_kernels.hip: through normalize(c), c = Su x Sv
-        const float nc = norm3(cx, cy, cz);
-        float gc0, gc1, gc2;
-        if (nc < 1e-12f) {
-            gc0 = g0 / 1e-12f; gc1 = g1 / 1e-12f; gc2 = g2 / 1e-12f;
-        } else {
-            const float inv = 1.0f / nc;
-            const float ux = cx * inv, uy = cy * inv, uz = cz * inv;
-            const float dot = ux * g0 + uy * g1 + uz * g2;
-            gc0 = (g0 - ux * dot) * inv; gc1 = (g1 - uy * dot) * inv; gc2 = (g2 - uz * dot) * inv;
-        }
-        go[0] = Sv[1] * gc2 - Sv[2] * gc1; go[1] = Sv[2] * gc0 - Sv[0] * gc2; go[2] = Sv[0] * gc1 - Sv[1] * gc0;
-        go[3] = gc1 * Su[2] - gc2 * Su[1]; go[4] = gc2 * Su[0] - gc0 * Su[2]; go[5] = gc0 * Su[1] - gc1 * Su[0];
-    }
-    if (a.points_out != nullptr) {
-        const int64_t out_row = (int64_t)b * a.N + *row;
-        a.points_out[out_row] = make_float4(px, py, pz, 1.0f);
-        a.normals_out[out_row] = make_float4(nx, ny, nz, 0.0f);
-    }
-}
-
-// Phase 2 for one (cell, r, s): the sorted positions j0 .. j1 - 1, in that order, contracted with Nu[r] Nv[s] (and the
-// derivatives) onto the running sums acc; position j's point gradient is at s_g + (j - g_first) * ng.  (Fetching the weights
-// of eight positions ahead of their adds was tried and was about a quarter slower at N = 20 000 and 80 000: DESIGN.md 4.7.)
-template <int DEG>
-__device__ __forceinline__ void fit_cell_sum(const float* tab, const float* s_g, const int ng, const bool fit_points, const int r,
-                                             const int s, const int j0, const int j1, const int g_first, float& acc0, float& acc1,
-                                             float& acc2)
-{
-    constexpr int S = FitRec<DEG>::S, W = FitRec<DEG>::W;
-    for (int j = j0; j < j1; ++j) {
-        const float* rec = tab + (int64_t)j * W;
-        const float* gj = s_g + (j - g_first) * ng;
-        if (fit_points) {
-            const float w00 = rec[2 + r] * rec[2 + 2 * S + s];
-            acc0 += w00 * gj[0]; acc1 += w00 * gj[1]; acc2 += w00 * gj[2];
-        } else {
-            const float w10 = rec[2 + S + r] * rec[2 + 2 * S + s], w01 = rec[2 + r] * rec[2 + 3 * S + s];
-            acc0 += w10 * gj[0] + w01 * gj[3]; acc1 += w10 * gj[1] + w01 * gj[4]; acc2 += w10 * gj[2] + w01 * gj[5];
-        }
-    }
-}
-
-// Phase 3: a control-point component adds the partials of the cells that touch it, in cell order, and hands the sum to own.
-template <typename Own>
-__device__ __forceinline__ void fit_gather(const FitArgs& a, const int p, const int q, const float* s_part, Own own)
-{
-    const int ncu = a.nu - p, ncv = a.nv - q, PQ = (p + 1) * (q + 1), ncp = a.nu * a.nv * 3;
-    for (int e = threadIdx.x; e < ncp; e += blockDim.x) {
-        const int cell = e / 3, k = e - 3 * cell;
-        const int ar = cell / a.nv, ac = cell - ar * a.nv;
-        float acc = 0.f;
-        for (int cu = max(0, ar - p); cu <= min(ar, ncu - 1); ++cu)
-            for (int cv = max(0, ac - q); cv <= min(ac, ncv - 1); ++cv)
-                acc += s_part[((cu * ncv + cv) * PQ + (ar - cu) * (q + 1) + (ac - cv)) * 3 + k];
-        own(e, acc);
-    }
-}
+// Where an epoch finds a facet's per-point data.  kFitLds: table and sorted targets staged in LDS; kFitStream: read from the
+// global buffers prepare wrote, every per-point array of the facet still in LDS; kFitChunked: streamed as well, and s_g / s_sq
+// hold one chunk of sorted positions (L is then the layout of ONE CHUNK: fit_layout with N = chunk).
+enum FitMode { kFitLds = 0, kFitStream = 1, kFitChunked = 2 };
 
 // One epoch's forward and backward for facet b with n valid points; the control net is in s_cp.  Calls own(e, g) once for every
 // control-point component e (by the thread that owns it) with its gradient g, and leaves the loss in lds[L.red] (valid after
 // the caller's next barrier).  The caller has synchronised the workgroup since s_cp was last written.
-template <int DEG, bool TAB_LDS, typename Own>
-__device__ __forceinline__ void fit_epoch(const FitArgs& a, const FitLayout& L, float* lds, int b, int n, Own own)
+//
+// Phases 1 and 2 run per chunk of `chunk` sorted positions (a multiple of 64); a resident facet is ONE chunk, positions 0 .. n,
+// and `chunk` is not read.  Every sum has the same order however the positions are chunked, so the result is the same bits: the
+// running sum of a (cell, r, s) is carried in s_part from chunk to chunk - a cell's points are consecutive positions, taken in
+// index order -, lane l of wave 0 carries its fp64 sum of the squared errors at positions l, l + 64, ... across the chunks (a
+// chunk starts at a multiple of 64, so the positions keep their lane), and the shuffle tree and phase 3 run once, after the
+// last chunk.  Only the cells that intersect a chunk have work in its phase 2.
+template <int DEG, FitMode MODE, typename Own>
+__device__ __forceinline__ void fit_epoch(const FitArgs& a, const FitLayout& L, float* lds, int b, int n, int chunk, Own own)
 {
     constexpr int S = FitRec<DEG>::S, W = FitRec<DEG>::W;
+    constexpr bool TAB_LDS = MODE == kFitLds, CHUNKED = MODE == kFitChunked;
     const int p = DEG > 0 ? DEG : a.p, q = DEG > 0 ? DEG : a.q;
     const int tid = threadIdx.x, T = blockDim.x;
     const int ncu = a.nu - p, ncv = a.nv - q, ncells = ncu * ncv, PQ = (p + 1) * (q + 1), ncp = a.nu * a.nv * 3;
@@ -258,79 +183,98 @@ __device__ __forceinline__ void fit_epoch(const FitArgs& a, const FitLayout& L, 
     const float4* tgt_g = reinterpret_cast<const float4*>(a.targets) + (int64_t)b * a.N;
     const float4* tgt_s = reinterpret_cast<const float4*>(lds + L.tgt);
 
-    // ---- phase 1: the points
     const float scale = (float)(2.0 / (4.0 * (double)n));          // MSELoss backward: (2 / numel) * (input - target)
-    for (int j = tid; j < n; j += T) {
-        const float* rec = tab + (int64_t)j * W;
-        float* go = s_g + j * ng;
-        float S0[4], Su[3], Sv[3];
-        fit_eval_point<DEG>(a, s_cp, rec, S0, Su, Sv);
-        // surfaces.py:615-661 (finish_point of nurbs_kernels.hip without canting)
-        const float cx = Su[1] * Sv[2] - Su[2] * Sv[1];
-        const float cy = Su[2] * Sv[0] - Su[0] * Sv[2];
-        const float cz = Su[0] * Sv[1] - Su[1] * Sv[0];
-        const float px = S0[0] / S0[3], py = S0[1] / S0[3], pz = S0[2] / S0[3];
-        const float ncl = fmaxf(norm3(cx, cy, cz), 1e-12f);
-        const float nx = cx / ncl, ny = cy / ncl, nz = cz / ncl;
-        float4 t;
-        if (TAB_LDS) t = tgt_s[j]; else t = tgt_g[perm[j]];
-        float e0, e1, e2, e3;
-        if (fit_points) { e0 = px - t.x; e1 = py - t.y; e2 = pz - t.z; e3 = 1.0f - t.w; }
-        else { e0 = nx - t.x; e1 = ny - t.y; e2 = nz - t.z; e3 = 0.0f - t.w; }
-        s_sq[j] = ((e0 * e0 + e1 * e1) + e2 * e2) + e3 * e3;
-        const float g0 = scale * e0, g1 = scale * e1, g2 = scale * e2;
-        if (fit_points) {
-            const float iw = 1.0f / S0[3];
-            go[0] = g0 * iw; go[1] = g1 * iw; go[2] = g2 * iw;
-        } else {
-            // point_adjoint of nurbs_kernels.hip: through normalize(c), c = Su x Sv
-            const float nc = norm3(cx, cy, cz);
-            float gc0, gc1, gc2;
-            if (nc < 1e-12f) {
-                gc0 = g0 / 1e-12f; gc1 = g1 / 1e-12f; gc2 = g2 / 1e-12f;
-            } else {
-                const float inv = 1.0f / nc;
-                const float ux = cx * inv, uy = cy * inv, uz = cz * inv;
-                const float dot = ux * g0 + uy * g1 + uz * g2;
-                gc0 = (g0 - ux * dot) * inv; gc1 = (g1 - uy * dot) * inv; gc2 = (g2 - uz * dot) * inv;
-            }
-            go[0] = Sv[1] * gc2 - Sv[2] * gc1; go[1] = Sv[2] * gc0 - Sv[0] * gc2; go[2] = Sv[0] * gc1 - Sv[1] * gc0;
-            go[3] = gc1 * Su[2] - gc2 * Su[1]; go[4] = gc2 * Su[0] - gc0 * Su[2]; go[5] = gc0 * Su[1] - gc1 * Su[0];
-        }
-        if (a.points_out != nullptr) {
-            const int64_t out_row = (int64_t)b * a.N + perm[j];
-            a.points_out[out_row] = make_float4(px, py, pz, 1.0f);
-            a.normals_out[out_row] = make_float4(nx, ny, nz, 0.0f);
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: the loss (wave 0 first), then one partial sum per (cell, r, s)
-    if (tid < 64) {
-        double acc = 0.0;
-        for (int j = tid; j < n; j += 64) acc += (double)s_sq[j];
-        acc = fit_wave_sum_f64(acc);
-        if (tid == 0) lds[L.red] = (float)(acc / (4.0 * (double)n));
-    }
-    for (int it = tid; it < ncells * PQ; it += T) {
-        const int c = it / PQ, rs = it - c * PQ;
-        const int r = rs / (q + 1), s = rs - r * (q + 1);
-        const int j0 = s_cells[c], j1 = s_cells[c + 1];
-        float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
-        for (int j = j0; j < j1; ++j) {
+    double sq_acc = 0.0;
+    // wave 0, once its lanes hold their sums over all positions: the fixed shuffle tree.  A resident facet has them in phase 2,
+    // ahead of the chains; the chunked epoch after its last chunk (inside the chunk loop the tree costs the compiler 36 B of
+    // scratch per lane in one instantiation).
+    auto loss_tree = [&]() {
+        const double sum = fit_wave_sum_f64(sq_acc);
+        if (tid == 0) lds[L.red] = (float)(sum / (4.0 * (double)n));
+    };
+    int first = 0;                                                  // position j's slot in s_g / s_sq is j - first
+    do {
+        const int last = CHUNKED ? min(first + chunk, n) : n;
+        // ---- phase 1: the chunk's points
+        for (int j = first + tid; j < last; j += T) {
             const float* rec = tab + (int64_t)j * W;
-            const float* gj = s_g + j * ng;
+            float* go = s_g + (j - first) * ng;
+            float S0[4], Su[3], Sv[3];
+            fit_eval_point<DEG>(a, s_cp, rec, S0, Su, Sv);
+            // surfaces.py:615-661 (finish_point of nurbs_kernels.hip without canting)
+            const float cx = Su[1] * Sv[2] - Su[2] * Sv[1];
+            const float cy = Su[2] * Sv[0] - Su[0] * Sv[2];
+            const float cz = Su[0] * Sv[1] - Su[1] * Sv[0];
+            const float px = S0[0] / S0[3], py = S0[1] / S0[3], pz = S0[2] / S0[3];
+            const float ncl = fmaxf(norm3(cx, cy, cz), 1e-12f);
+            const float nx = cx / ncl, ny = cy / ncl, nz = cz / ncl;
+            float4 t;
+            if (TAB_LDS) t = tgt_s[j]; else t = tgt_g[perm[j]];
+            float e0, e1, e2, e3;
+            if (fit_points) { e0 = px - t.x; e1 = py - t.y; e2 = pz - t.z; e3 = 1.0f - t.w; }
+            else { e0 = nx - t.x; e1 = ny - t.y; e2 = nz - t.z; e3 = 0.0f - t.w; }
+            s_sq[j - first] = ((e0 * e0 + e1 * e1) + e2 * e2) + e3 * e3;
+            const float g0 = scale * e0, g1 = scale * e1, g2 = scale * e2;
             if (fit_points) {
-                const float w00 = rec[2 + r] * rec[2 + 2 * S + s];
-                acc0 += w00 * gj[0]; acc1 += w00 * gj[1]; acc2 += w00 * gj[2];
+                const float iw = 1.0f / S0[3];
+                go[0] = g0 * iw; go[1] = g1 * iw; go[2] = g2 * iw;
             } else {
-                const float w10 = rec[2 + S + r] * rec[2 + 2 * S + s], w01 = rec[2 + r] * rec[2 + 3 * S + s];
-                acc0 += w10 * gj[0] + w01 * gj[3]; acc1 += w10 * gj[1] + w01 * gj[4]; acc2 += w10 * gj[2] + w01 * gj[5];
+                // point_adjoint of nurbs_kernels.hip: through normalize(c), c = Su x Sv
+                const float nc = norm3(cx, cy, cz);
+                float gc0, gc1, gc2;
+                if (nc < 1e-12f) {
+                    gc0 = g0 / 1e-12f; gc1 = g1 / 1e-12f; gc2 = g2 / 1e-12f;
+                } else {
+                    const float inv = 1.0f / nc;
+                    const float ux = cx * inv, uy = cy * inv, uz = cz * inv;
+                    const float dot = ux * g0 + uy * g1 + uz * g2;
+                    gc0 = (g0 - ux * dot) * inv; gc1 = (g1 - uy * dot) * inv; gc2 = (g2 - uz * dot) * inv;
+                }
+                go[0] = Sv[1] * gc2 - Sv[2] * gc1; go[1] = Sv[2] * gc0 - Sv[0] * gc2; go[2] = Sv[0] * gc1 - Sv[1] * gc0;
+                go[3] = gc1 * Su[2] - gc2 * Su[1]; go[4] = gc2 * Su[0] - gc0 * Su[2]; go[5] = gc0 * Su[1] - gc1 * Su[0];
+            }
+            if (a.points_out != nullptr) {
+                const int64_t out_row = (int64_t)b * a.N + perm[j];
+                a.points_out[out_row] = make_float4(px, py, pz, 1.0f);
+                a.normals_out[out_row] = make_float4(nx, ny, nz, 0.0f);
             }
         }
-        s_part[it * 3] = acc0; s_part[it * 3 + 1] = acc1; s_part[it * 3 + 2] = acc2;
-    }
-    __syncthreads();
+        __syncthreads();
+
+        // ---- phase 2: the loss (wave 0 first), then one running sum per (cell, r, s)
+        if (tid < 64) {
+            for (int j = first + tid; j < last; j += 64) sq_acc += (double)s_sq[j - first];
+            if (!CHUNKED) loss_tree();
+        }
+        for (int it = tid; it < ncells * PQ; it += T) {
+            const int c = it / PQ, rs = it - c * PQ;
+            const int r = rs / (q + 1), s = rs - r * (q + 1);
+            const int j0 = CHUNKED ? max(s_cells[c], first) : s_cells[c];
+            const int j1 = CHUNKED ? min(s_cells[c + 1], last) : s_cells[c + 1];
+            float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
+            if (first > 0) {                                        // a later chunk: nothing to add, or the sum so far
+                if (j0 >= j1) continue;
+                acc0 = s_part[it * 3]; acc1 = s_part[it * 3 + 1]; acc2 = s_part[it * 3 + 2];
+            }
+            // (fetching the weights of eight positions ahead of their adds was tried and was about a quarter slower at
+            // N = 20 000 and 80 000: DESIGN.md 4.7)
+            for (int j = j0; j < j1; ++j) {
+                const float* rec = tab + (int64_t)j * W;
+                const float* gj = s_g + (j - first) * ng;
+                if (fit_points) {
+                    const float w00 = rec[2 + r] * rec[2 + 2 * S + s];
+                    acc0 += w00 * gj[0]; acc1 += w00 * gj[1]; acc2 += w00 * gj[2];
+                } else {
+                    const float w10 = rec[2 + S + r] * rec[2 + 2 * S + s], w01 = rec[2 + r] * rec[2 + 3 * S + s];
+                    acc0 += w10 * gj[0] + w01 * gj[3]; acc1 += w10 * gj[1] + w01 * gj[4]; acc2 += w10 * gj[2] + w01 * gj[5];
+                }
+            }
+            s_part[it * 3] = acc0; s_part[it * 3 + 1] = acc1; s_part[it * 3 + 2] = acc2;
+        }
+        __syncthreads();
+        first += chunk;
+    } while (CHUNKED && first < n);
+    if (CHUNKED && tid < 64) loss_tree();
 
     // ---- phase 3: a control-point component adds the partials of the cells that touch it, in cell order
     for (int e = tid; e < ncp; e += T) {
@@ -344,73 +288,16 @@ __device__ __forceinline__ void fit_epoch(const FitArgs& a, const FitLayout& L, 
     }
 }
 
-// The same epoch when a facet's per-point arrays do not fit in LDS: s_g and s_sq hold one chunk of `chunk` sorted positions (a
-// multiple of 64), table and targets are streamed from global memory.  Every sum keeps the order fit_epoch gives it, so the
-// result is the same bits: the running sum of a (cell, r, s) is carried in s_part from chunk to chunk - a cell's points are
-// consecutive positions, taken in index order -, lane l of wave 0 carries its fp64 sum of the squared errors at positions
-// l, l + 64, ... across the chunks (a chunk starts at a multiple of 64, so the positions keep their lane), and the shuffle tree
-// and phase 3 run once, after the last chunk.  Only the cells that intersect a chunk have work in its phase 2.
-template <int DEG, typename Own>
-__device__ __forceinline__ void fit_epoch_chunked(const FitArgs& a, const FitLayout& L, float* lds, int b, int n, int chunk, Own own)
-{
-    constexpr int W = FitRec<DEG>::W;
-    const int p = DEG > 0 ? DEG : a.p, q = DEG > 0 ? DEG : a.q;
-    const int tid = threadIdx.x, T = blockDim.x;
-    const int ncells = (a.nu - p) * (a.nv - q), PQ = (p + 1) * (q + 1);
-    const bool fit_points = a.method == ART_FIT_POINTS;
-    const int ng = fit_points ? 3 : 6;
-    const float* s_cp = lds + L.cp;
-    float* s_part = lds + L.part;
-    float* s_g = lds + L.g;
-    float* s_sq = lds + L.sq;
-    const int* s_cells = reinterpret_cast<const int*>(lds + L.cells);
-    const float* tab = a.table + (int64_t)b * a.N * W;
-    const int32_t* perm = a.perm + (int64_t)b * a.N;
-    const float4* tgt_g = reinterpret_cast<const float4*>(a.targets) + (int64_t)b * a.N;
-
-    // (each running sum is started, carried and finished by one thread; the barrier is for a facet without points)
-    for (int it = tid; it < ncells * PQ; it += T) { s_part[it * 3] = 0.f; s_part[it * 3 + 1] = 0.f; s_part[it * 3 + 2] = 0.f; }
-    __syncthreads();
-    const float scale = (float)(2.0 / (4.0 * (double)n));
-    double sq_acc = 0.0;
-    for (int first = 0; first < n; first += chunk) {
-        const int last = min(first + chunk, n);
-        // ---- phase 1: the chunk's points
-        for (int j = first + tid; j < last; j += T)
-            fit_point<DEG>(a, s_cp, tab + (int64_t)j * W, tgt_g[perm[j]], scale, b, perm + j, s_g + (j - first) * ng, s_sq + (j - first));
-        __syncthreads();
-        // ---- phase 2: the chunk's share of the loss and of the cells that reach into it
-        if (tid < 64)
-            for (int j = first + tid; j < last; j += 64) sq_acc += (double)s_sq[j - first];
-        for (int it = tid; it < ncells * PQ; it += T) {
-            const int c = it / PQ, rs = it - c * PQ;
-            const int j0 = max(s_cells[c], first), j1 = min(s_cells[c + 1], last);
-            if (j0 >= j1) continue;
-            const int r = rs / (q + 1), s = rs - r * (q + 1);
-            float acc0 = s_part[it * 3], acc1 = s_part[it * 3 + 1], acc2 = s_part[it * 3 + 2];
-            fit_cell_sum<DEG>(tab, s_g, ng, fit_points, r, s, j0, j1, first, acc0, acc1, acc2);
-            s_part[it * 3] = acc0; s_part[it * 3 + 1] = acc1; s_part[it * 3 + 2] = acc2;
-        }
-        __syncthreads();
-    }
-    if (tid < 64) {
-        sq_acc = fit_wave_sum_f64(sq_acc);
-        if (tid == 0) lds[L.red] = (float)(sq_acc / (4.0 * (double)n));
-    }
-    // ---- phase 3
-    fit_gather(a, p, q, s_part, own);
-}
-
 // Stage what an epoch reads besides the control net: the cell offsets, and - when they live in LDS - the table and the targets
 // in sorted order.  Followed by the caller's barrier.
-template <int DEG, bool TAB_LDS>
+template <int DEG, FitMode MODE>
 __device__ __forceinline__ void fit_stage(const FitArgs& a, const FitLayout& L, float* lds, int b, int n)
 {
     constexpr int W = FitRec<DEG>::W;
     const int ncells = (a.nu - a.p) * (a.nv - a.q);
     int* s_cells = reinterpret_cast<int*>(lds + L.cells);
     for (int i = threadIdx.x; i <= ncells; i += blockDim.x) s_cells[i] = min(max(a.cell_start[(int64_t)b * (ncells + 1) + i], 0), n);
-    if (TAB_LDS) {
+    if (MODE == kFitLds) {
         const float* g_tab = a.table + (int64_t)b * a.N * W;
         for (int i = threadIdx.x; i < n * W; i += blockDim.x) lds[L.tab + i] = g_tab[i];
         const float4* tgt_g = reinterpret_cast<const float4*>(a.targets) + (int64_t)b * a.N;
@@ -459,87 +346,24 @@ __device__ __forceinline__ void fit_plateau_step(const FitArgs& a, float loss, d
     }
 }
 
-template <int DEG, bool TAB_LDS>
-__global__ __launch_bounds__(kFitMaxBlock) void surface_fit_loss_grad_kernel(FitArgs a, FitLayout L)
+// The two kernels, one instantiation per degree and FitMode.  `chunk` (kFitChunked only) is the last argument, behind what the
+// resident launches have always passed.
+template <int DEG, FitMode MODE>
+__global__ __launch_bounds__(kFitMaxBlock) void surface_fit_loss_grad_kernel(FitArgs a, FitLayout L, int chunk)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = blockIdx.x, ncp = a.nu * a.nv * 3;
     const int n = fit_n_valid(a, b);
     for (int i = threadIdx.x; i < ncp; i += blockDim.x) lds[L.cp + i] = a.cp_in[(int64_t)b * ncp + i];
-    fit_stage<DEG, TAB_LDS>(a, L, lds, b, n);
+    fit_stage<DEG, MODE>(a, L, lds, b, n);
     __syncthreads();
     float* out = a.grad + (int64_t)b * ncp;
-    fit_epoch<DEG, TAB_LDS>(a, L, lds, b, n, [&](int e, float g) { out[e] = g; });
-    if (threadIdx.x == 0) a.loss[b] = lds[L.red];      // (written by this thread before the barrier between phases 2 and 3)
-}
-
-template <int DEG, bool TAB_LDS>
-__global__ __launch_bounds__(kFitMaxBlock) void surface_fit_run_kernel(FitArgs a, FitLayout L)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int b = blockIdx.x, ncp = a.nu * a.nv * 3, tid = threadIdx.x, T = blockDim.x;
-    const int n = fit_n_valid(a, b);
-    // the facet's scalars: every thread holds its own copy, all evolve alike
-    double lr = a.sf64[2 * (int64_t)b], best = a.sf64[2 * (int64_t)b + 1];
-    const int32_t* si = a.si32 + 5 * (int64_t)b;
-    int step = si[0], num_bad = si[1], cool = si[2], epochs_run = si[3], done = si[4];
-    float last = a.last_loss[b];
-    float *s_cp = lds + L.cp, *s_m = lds + L.m, *s_v = lds + L.v;
-    double* s_bc1 = reinterpret_cast<double*>(lds + L.bc1);
-    float* s_ibc2 = lds + L.ibc2;
-    for (int i = tid; i < ncp; i += T) {
-        s_cp[i] = a.cp[(int64_t)b * ncp + i]; s_m[i] = a.m[(int64_t)b * ncp + i]; s_v[i] = a.v[(int64_t)b * ncp + i];
-    }
-    // bias corrections of this launch's steps (torch/optim/adam.py: 1 - beta ** step in double), one step per thread
-    for (int i = tid; i < a.epochs; i += T) {
-        const double st = (double)(step + 1 + i);
-        s_bc1[i] = 1.0 - pow(a.beta1d, st);
-        s_ibc2[i] = (float)(1.0 / sqrt(1.0 - pow(a.beta2d, st)));
-    }
-    fit_stage<DEG, TAB_LDS>(a, L, lds, b, n);
-    __syncthreads();
-    for (int it = 0; it < a.epochs && !done; ++it) {
-        if (!(last > a.tolerance) || epochs_run > a.max_epoch) { done = 1; break; }     // surface_generator.py:196
-        const float step_size = (float)(lr / s_bc1[it]);
-        const float inv_bc2_sqrt = s_ibc2[it];
-        fit_epoch<DEG, TAB_LDS>(a, L, lds, b, n, [&](int e, float g) {
-            fit_adam_element(a, s_cp, s_m, s_v, e, g, step_size, inv_bc2_sqrt);
-        });
-        __syncthreads();
-        const float loss = lds[L.red];
-        if (a.sched) fit_plateau_step(a, loss, lr, best, num_bad, cool);
-        last = loss; epochs_run += 1; step += 1;
-    }
-    if (!done && (!(last > a.tolerance) || epochs_run > a.max_epoch)) done = 1;
-    for (int i = tid; i < ncp; i += T) {
-        a.cp[(int64_t)b * ncp + i] = s_cp[i]; a.m[(int64_t)b * ncp + i] = s_m[i]; a.v[(int64_t)b * ncp + i] = s_v[i];
-    }
-    if (tid == 0) {
-        a.sf64[2 * (int64_t)b] = lr; a.sf64[2 * (int64_t)b + 1] = best;
-        int32_t* so = a.si32 + 5 * (int64_t)b;
-        so[0] = step; so[1] = num_bad; so[2] = cool; so[3] = epochs_run; so[4] = done;
-        a.last_loss[b] = last;
-    }
-}
-
-// The two kernels above for a facet taken in chunks of `chunk` sorted positions: L is the layout of ONE CHUNK (fit_layout with
-// N = chunk, the table in global memory), the epoch is fit_epoch_chunked, everything around it is what it is above.
-template <int DEG>
-__global__ __launch_bounds__(kFitMaxBlock) void surface_fit_loss_grad_chunked_kernel(FitArgs a, FitLayout L, int chunk)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int b = blockIdx.x, ncp = a.nu * a.nv * 3;
-    const int n = fit_n_valid(a, b);
-    for (int i = threadIdx.x; i < ncp; i += blockDim.x) lds[L.cp + i] = a.cp_in[(int64_t)b * ncp + i];
-    fit_stage<DEG, false>(a, L, lds, b, n);
-    __syncthreads();
-    float* out = a.grad + (int64_t)b * ncp;
-    fit_epoch_chunked<DEG>(a, L, lds, b, n, chunk, [&](int e, float g) { out[e] = g; });
+    fit_epoch<DEG, MODE>(a, L, lds, b, n, chunk, [&](int e, float g) { out[e] = g; });
     if (threadIdx.x == 0) a.loss[b] = lds[L.red];      // (written by this thread, before phase 3)
 }
 
-template <int DEG>
-__global__ __launch_bounds__(kFitMaxBlock) void surface_fit_run_chunked_kernel(FitArgs a, FitLayout L, int chunk)
+template <int DEG, FitMode MODE>
+__global__ __launch_bounds__(kFitMaxBlock) void surface_fit_run_kernel(FitArgs a, FitLayout L, int chunk)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = blockIdx.x, ncp = a.nu * a.nv * 3, tid = threadIdx.x, T = blockDim.x;
@@ -561,13 +385,13 @@ __global__ __launch_bounds__(kFitMaxBlock) void surface_fit_run_chunked_kernel(F
         s_bc1[i] = 1.0 - pow(a.beta1d, st);
         s_ibc2[i] = (float)(1.0 / sqrt(1.0 - pow(a.beta2d, st)));
     }
-    fit_stage<DEG, false>(a, L, lds, b, n);
+    fit_stage<DEG, MODE>(a, L, lds, b, n);
     __syncthreads();
     for (int it = 0; it < a.epochs && !done; ++it) {
         if (!(last > a.tolerance) || epochs_run > a.max_epoch) { done = 1; break; }     // surface_generator.py:196
         const float step_size = (float)(lr / s_bc1[it]);
         const float inv_bc2_sqrt = s_ibc2[it];
-        fit_epoch_chunked<DEG>(a, L, lds, b, n, chunk, [&](int e, float g) {
+        fit_epoch<DEG, MODE>(a, L, lds, b, n, chunk, [&](int e, float g) {
             fit_adam_element(a, s_cp, s_m, s_v, e, g, step_size, inv_bc2_sqrt);
         });
         __syncthreads();
@@ -603,8 +427,7 @@ __device__ __forceinline__ float fit_linspace(float start, float end, int steps,
     return i < steps / 2 ? __fmaf_rn(step, (float)i, start) : __fmaf_rn(-step, (float)(steps - i - 1), end);
 }
 
-// ---- the stages of surface_fit_prepare_kernel (below, kept as it was written) as functions for the tiled kernel: the same
-// expressions, the same values.
+// ---- the stages both prepare kernels are written with
 //
 // What a facet's rows are normalised with: the minima of the e and n columns and the denominators of normalize_points.
 struct PrepFrame { float mn_e, mn_n, den_e, den_n; };
@@ -699,10 +522,10 @@ template <int DEG>
 __global__ __launch_bounds__(kFitPrepBlock) void surface_fit_prepare_kernel(PrepArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int S = FitRec<DEG>::S, W = FitRec<DEG>::W;
+    constexpr int W = FitRec<DEG>::W;
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
     const int p = DEG > 0 ? DEG : a.p, q = DEG > 0 ? DEG : a.q;
-    const int ncu = a.nu - p, ncv = a.nv - q, ncells = ncu * ncv, nku = a.nu + p + 1, nkv = a.nv + q + 1;
+    const int ncells = (a.nu - p) * (a.nv - q), nku = a.nu + p + 1, nkv = a.nv + q + 1;
     const int n = a.n_valid != nullptr ? min(max(a.n_valid[b], 0), a.N) : a.N;
     int* s_cell = reinterpret_cast<int*>(lds);
     int* s_perm = s_cell + a.N;
@@ -711,46 +534,13 @@ __global__ __launch_bounds__(kFitPrepBlock) void surface_fit_prepare_kernel(Prep
     float* s_kv = s_ku + nku;
     float* s_ext = s_kv + nkv;
     const float4* tp = reinterpret_cast<const float4*>(a.targets_points) + (int64_t)b * a.N;
-    for (int i = tid; i < nku; i += T) s_ku[i] = a.knots_u[i];
-    for (int i = tid; i < nkv; i += T) s_kv[i] = a.knots_v[i];
-    // extrema of the e and n columns over the valid rows (order does not matter for min / max)
-    float mn_e = INFINITY, mx_e = -INFINITY, mn_n = INFINITY, mx_n = -INFINITY;
-    for (int i = tid; i < n; i += T) {
-        const float4 x = tp[i];
-        mn_e = fminf(mn_e, x.x); mx_e = fmaxf(mx_e, x.x); mn_n = fminf(mn_n, x.y); mx_n = fmaxf(mx_n, x.y);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn_e = fminf(mn_e, __shfl_down(mn_e, off, 64)); mx_e = fmaxf(mx_e, __shfl_down(mx_e, off, 64));
-        mn_n = fminf(mn_n, __shfl_down(mn_n, off, 64)); mx_n = fmaxf(mx_n, __shfl_down(mx_n, off, 64));
-    }
-    if ((tid & 63) == 0) { float* e = s_ext + 4 * (tid >> 6); e[0] = mn_e; e[1] = mx_e; e[2] = mn_n; e[3] = mx_n; }
-    __syncthreads();
-    mn_e = s_ext[0]; mx_e = s_ext[1]; mn_n = s_ext[2]; mx_n = s_ext[3];
-    for (int w = 1; w < T / 64; ++w) {
-        mn_e = fminf(mn_e, s_ext[4 * w]); mx_e = fmaxf(mx_e, s_ext[4 * w + 1]);
-        mn_n = fminf(mn_n, s_ext[4 * w + 2]); mx_n = fmaxf(mx_n, s_ext[4 * w + 3]);
-    }
-    // the initial net (surface_generator.py:148-174)
-    const float width = n > 0 ? mx_e - mn_e : 0.0f, height = n > 0 ? mx_n - mn_n : 0.0f;      // (no valid rows: a zero net)
-    float* cp = a.cp + (int64_t)b * a.nu * a.nv * 3;
-    for (int i = tid; i < a.nu * a.nv; i += T) {
-        const int r = i / a.nv, c = i - r * a.nv;
-        cp[3 * i] = fit_linspace(-width / 2.0f, width / 2.0f, a.nu, r);
-        cp[3 * i + 1] = fit_linspace(-height / 2.0f, height / 2.0f, a.nv, c);
-        cp[3 * i + 2] = 0.0f;
-    }
-    // coordinates.normalize_points: (x - min + 1e-5) / max(x - min + 2e-5); the maximum is taken at the largest x (monotone)
-    const float den_e = (mx_e - mn_e) + 2e-5f, den_n = (mx_n - mn_n) + 2e-5f;
+    const PrepFrame f = fit_prep_frame<DEG>(a, b, n, s_ku, s_kv, s_ext);
     float2* uv = reinterpret_cast<float2*>(a.eval_uv) + (int64_t)b * a.N;
     for (int i = tid; i < a.N; i += T) {
         float2 x = make_float2(0.f, 0.f);
         if (i < n) {
-            const float4 t = tp[i];
-            x.x = ((t.x - mn_e) + 1e-5f) / den_e;
-            x.y = ((t.y - mn_n) + 1e-5f) / den_n;
-            const int su = find_span(x.x, s_ku, a.nu, p, 1, ncu + 1), sv = find_span(x.y, s_kv, a.nv, q, 1, ncv + 1);
-            s_cell[i] = (su - p) * ncv + (sv - q);
+            x = fit_prep_uv(f, tp[i]);
+            s_cell[i] = fit_prep_cell<DEG>(a, x, s_ku, s_kv);
         }
         uv[i] = x;
     }
@@ -783,24 +573,7 @@ __global__ __launch_bounds__(kFitPrepBlock) void surface_fit_prepare_kernel(Prep
             for (int k = 0; k < W; ++k) rec[k] = 0.0f;
             continue;
         }
-        const int i = s_perm[j];
-        const float4 t = tp[i];
-        const float u = ((t.x - mn_e) + 1e-5f) / den_e, v = ((t.y - mn_n) + 1e-5f) / den_n;
-        const int su = find_span(u, s_ku, a.nu, p, 1, ncu + 1), sv = find_span(v, s_kv, a.nv, q, 1, ncv + 1);
-        float Nu[S], Du[S], Nv[S], Dv[S];
-        basis<DEG>(u, s_ku, su, p, Nu, Du);
-        basis<DEG>(v, s_kv, sv, q, Nv, Dv);
-        rec[0] = __int_as_float(su | (sv << 16));
-        float wsum = 0.f;
-#pragma unroll
-        for (int r = 0; r < S; ++r) {
-            const bool in_u = r <= p, in_v = r <= q;
-            if (in_u) wsum += Nu[r] * 1.0f;      // the homogeneous coordinate's inner sum (line_basis of nurbs_kernels.hip)
-            rec[2 + r] = in_u ? Nu[r] : 0.0f; rec[2 + S + r] = in_u ? Du[r] : 0.0f;
-            rec[2 + 2 * S + r] = in_v ? Nv[r] : 0.0f; rec[2 + 3 * S + r] = in_v ? Dv[r] : 0.0f;
-        }
-        rec[1] = wsum;
-        rec[2 + 4 * S] = __int_as_float(s_cell[i]);
+        fit_prep_table_row<DEG>(a, f, tp[s_perm[j]], s_ku, s_kv, rec);
     }
 }
 
@@ -890,41 +663,27 @@ bool fit_shape_ok(int64_t B, int64_t N, int64_t nu, int64_t nv, int p, int q)
 
 using namespace art;
 
-// KERNEL<DEG, TAB_LDS> for the degrees of `a` and the table's place; more than 64 KB of dynamic LDS has to be asked for.
-#define ART_FIT_LAUNCH(KERNEL, DEG, TAB, blocks, block, lds, stream, ...)                                                      \
+// A launch with dynamic LDS: more than 64 KB of it has to be asked for.
+template <typename... Params>
+static int fit_launch(void (*kernel)(Params...), int64_t blocks, int block, size_t lds, hipStream_t stream, Params... args)
+{
+    ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(block), lds, stream, args...);
+    ART_HIP(hipGetLastError());
+    return ART_OK;
+}
+
+// The statement(s) after `deg` with DEG the kernels' instantiation for deg = fit_deg(p, q): 2, 3, or 0 (degrees read at run time).
+#define ART_FIT_BY_DEGREE(deg, ...)                                                                                            \
     do {                                                                                                                       \
-        ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL<DEG, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)(lds)));                                                                              \
-        hipLaunchKernelGGL((KERNEL<DEG, TAB>), dim3((unsigned)(blocks)), dim3(block), lds, stream, __VA_ARGS__);               \
+        if ((deg) == 2) { constexpr int DEG = 2; __VA_ARGS__; }                                                                \
+        else if ((deg) == 3) { constexpr int DEG = 3; __VA_ARGS__; }                                                           \
+        else { constexpr int DEG = 0; __VA_ARGS__; }                                                                           \
     } while (0)
 
-#define ART_FIT_DISPATCH(KERNEL, deg, tab_lds, blocks, block, lds, stream, ...)                                                \
-    do {                                                                                                                       \
-        if (tab_lds) {                                                                                                         \
-            if ((deg) == 2) ART_FIT_LAUNCH(KERNEL, 2, true, blocks, block, lds, stream, __VA_ARGS__);                          \
-            else if ((deg) == 3) ART_FIT_LAUNCH(KERNEL, 3, true, blocks, block, lds, stream, __VA_ARGS__);                     \
-            else ART_FIT_LAUNCH(KERNEL, 0, true, blocks, block, lds, stream, __VA_ARGS__);                                     \
-        } else {                                                                                                               \
-            if ((deg) == 2) ART_FIT_LAUNCH(KERNEL, 2, false, blocks, block, lds, stream, __VA_ARGS__);                         \
-            else if ((deg) == 3) ART_FIT_LAUNCH(KERNEL, 3, false, blocks, block, lds, stream, __VA_ARGS__);                    \
-            else ART_FIT_LAUNCH(KERNEL, 0, false, blocks, block, lds, stream, __VA_ARGS__);                                    \
-        }                                                                                                                      \
-    } while (0)
-
-// The chunked kernels: KERNEL<DEG>, the table always streamed.
-#define ART_FIT_LAUNCH_CHUNKED(KERNEL, DEG, blocks, block, lds, stream, ...)                                                   \
-    do {                                                                                                                       \
-        ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL<DEG>), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                    (int)(lds)));                                                                              \
-        hipLaunchKernelGGL((KERNEL<DEG>), dim3((unsigned)(blocks)), dim3(block), lds, stream, __VA_ARGS__);                    \
-    } while (0)
-
-#define ART_FIT_DISPATCH_CHUNKED(KERNEL, deg, blocks, block, lds, stream, ...)                                                 \
-    do {                                                                                                                       \
-        if ((deg) == 2) ART_FIT_LAUNCH_CHUNKED(KERNEL, 2, blocks, block, lds, stream, __VA_ARGS__);                            \
-        else if ((deg) == 3) ART_FIT_LAUNCH_CHUNKED(KERNEL, 3, blocks, block, lds, stream, __VA_ARGS__);                       \
-        else ART_FIT_LAUNCH_CHUNKED(KERNEL, 0, blocks, block, lds, stream, __VA_ARGS__);                                       \
-    } while (0)
+// KERNEL<DEG, mode> of run / loss_grad
+#define ART_FIT_BY_MODE(KERNEL, DEG, mode)                                                                                     \
+    ((mode) == kFitLds ? KERNEL<DEG, kFitLds> : (mode) == kFitStream ? KERNEL<DEG, kFitStream> : KERNEL<DEG, kFitChunked>)
 
 extern "C" int64_t art_surface_fit_table_words(int p, int q)
 {
@@ -952,16 +711,7 @@ extern "C" int art_surface_fit_prepare(const float* targets_points, const int32_
     const int deg = fit_deg(p, q);
     size_t lds = sizeof(float) * (size_t)(2 * N + ncells + 1 + small);
     if (knob <= 0 && N <= kFitResidentMaxN && (int64_t)lds <= kFitLdsBudget) {
-#define ART_FIT_PREP(DEG)                                                                                                      \
-    do {                                                                                                                       \
-        ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&surface_fit_prepare_kernel<DEG>),                           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
-        hipLaunchKernelGGL(surface_fit_prepare_kernel<DEG>, dim3((unsigned)B), dim3(kFitPrepBlock), lds, stream, a);           \
-    } while (0)
-        if (deg == 2) ART_FIT_PREP(2);
-        else if (deg == 3) ART_FIT_PREP(3);
-        else ART_FIT_PREP(0);
-#undef ART_FIT_PREP
+        ART_FIT_BY_DEGREE(deg, return fit_launch(surface_fit_prepare_kernel<DEG>, B, kFitPrepBlock, lds, stream, a));
     } else {
         // the rows in tiles: what stays in LDS is at most 2 * 4096 + 1 offsets and 2 * (4096 + 8) knots, so a tile always fits
         const int64_t fixed = 2 * ncells + 1 + small;
@@ -969,27 +719,17 @@ extern "C" int art_surface_fit_prepare(const float* targets_points, const int32_
         if (knob > 0) tile = std::min<int64_t>(tile, ((int64_t)knob + 63) / 64 * 64);
         if (tile < 64) return ART_EUNSUPPORTED;
         lds = sizeof(float) * (size_t)(tile + fixed);
-#define ART_FIT_PREP(DEG)                                                                                                      \
-    do {                                                                                                                       \
-        ART_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&surface_fit_prepare_tiled_kernel<DEG>),                     \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
-        hipLaunchKernelGGL(surface_fit_prepare_tiled_kernel<DEG>, dim3((unsigned)B), dim3(kFitPrepBlock), lds, stream, a,      \
-                           (int)tile);                                                                                         \
-    } while (0)
-        if (deg == 2) ART_FIT_PREP(2);
-        else if (deg == 3) ART_FIT_PREP(3);
-        else ART_FIT_PREP(0);
-#undef ART_FIT_PREP
+        ART_FIT_BY_DEGREE(deg,
+                          return fit_launch(surface_fit_prepare_tiled_kernel<DEG>, B, kFitPrepBlock, lds, stream, a, (int)tile));
     }
-    ART_HIP(hipGetLastError());
-    return ART_OK;
 }
 
 // Fills what loss_grad and run share; decides where the table lives and, when a facet's per-point arrays do not fit in LDS
-// beside the net's block, the chunk length (*chunk > 0: the chunked kernels, L is one chunk's layout).  Returns an error code.
+// beside the net's block, the chunk length (kFitChunked: L is one chunk's layout); *block is the workgroup size.  Returns an
+// error code.
 static int fit_common(FitArgs& a, FitLayout& L, const float* targets, const int32_t* n_valid, const int32_t* perm,
                       const int32_t* cell_start, const float* table, int64_t B, int64_t N, int64_t nu, int64_t nv, int p, int q,
-                      int method, int epochs, bool* tab_lds, int* chunk)
+                      int method, int epochs, FitMode* mode, int* chunk, int* block)
 {
     *chunk = 0;
     if (!fit_shape_ok(B, N, nu, nv, p, q) || (method != ART_FIT_POINTS && method != ART_FIT_NORMALS)) return ART_EINVAL;
@@ -1010,14 +750,16 @@ static int fit_common(FitArgs& a, FitLayout& L, const float* targets, const int3
         if (net * 4 > kFitLdsBudget || C < 64) return ART_EUNSUPPORTED;
         C = std::min<int64_t>(C, (N + 63) / 64 * 64);
         if (knob > 0) C = std::min<int64_t>(C, ((int64_t)knob + 63) / 64 * 64);
-        *tab_lds = false;
+        *mode = kFitChunked;
         *chunk = (int)C;
+        *block = fit_block(std::min<int64_t>(N, C));
         L = fit_layout((int)C, (int)nu, (int)nv, p, q, method, W, epochs, false);
         if ((int64_t)L.total * 4 > kFitLdsBudget) return ART_EUNSUPPORTED;
         return ART_OK;
     }
-    *tab_lds =(fixed + N * (4 + W)) * 4 <= kFitLdsBudget && debug_env_int("ARTIST_HIP_FIT_STREAM", 0) == 0;
-    L = fit_layout((int)N, (int)nu, (int)nv, p, q, method, W, epochs, *tab_lds);
+    *mode = (fixed + N * (4 + W)) * 4 <= kFitLdsBudget && debug_env_int("ARTIST_HIP_FIT_STREAM", 0) == 0 ? kFitLds : kFitStream;
+    *block = fit_block(N);
+    L = fit_layout((int)N, (int)nu, (int)nv, p, q, method, W, epochs, *mode == kFitLds);
     if ((int64_t)L.total * 4 > kFitLdsBudget) return ART_EUNSUPPORTED;
     return ART_OK;
 }
@@ -1030,19 +772,17 @@ extern "C" int art_surface_fit_loss_grad(const float* control_points, const floa
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     FitArgs a;
     FitLayout L;
-    bool tab_lds = false;
-    int chunk = 0;
-    const int rc = fit_common(a, L, targets, n_valid, perm, cell_start, table, B, N, nu, nv, p, q, method, 0, &tab_lds, &chunk);
+    FitMode mode = kFitLds;
+    int chunk = 0, block = 0;
+    const int rc = fit_common(a, L, targets, n_valid, perm, cell_start, table, B, N, nu, nv, p, q, method, 0, &mode, &chunk, &block);
     if (rc != ART_OK) return rc;
     if (B == 0) return ART_OK;
     if (!control_points || !loss || !grad_control_points || (points_out == nullptr) != (normals_out == nullptr)) return ART_EINVAL;
     a.cp_in = control_points; a.loss = loss; a.grad = grad_control_points;
     a.points_out = reinterpret_cast<float4*>(points_out); a.normals_out = reinterpret_cast<float4*>(normals_out);
     const size_t lds = (size_t)L.total * sizeof(float);
-    if (chunk > 0) ART_FIT_DISPATCH_CHUNKED(surface_fit_loss_grad_chunked_kernel, fit_deg(p, q), B, fit_block(std::min<int64_t>(N, chunk)), lds, stream, a, L, chunk);
-    else ART_FIT_DISPATCH(surface_fit_loss_grad_kernel, fit_deg(p, q), tab_lds, B, fit_block(N), lds, stream, a, L);
-    ART_HIP(hipGetLastError());
-    return ART_OK;
+    ART_FIT_BY_DEGREE(fit_deg(p, q),
+                      return fit_launch(ART_FIT_BY_MODE(surface_fit_loss_grad_kernel, DEG, mode), B, block, lds, stream, a, L, chunk));
 }
 
 extern "C" int art_surface_fit_run(float* control_points, float* exp_avg, float* exp_avg_sq, double* state_f64,
@@ -1062,9 +802,9 @@ extern "C" int art_surface_fit_run(float* control_points, float* exp_avg, float*
         return ART_EINVAL;
     FitArgs a;
     FitLayout L;
-    bool tab_lds = false;
-    int chunk = 0;
-    const int rc = fit_common(a, L, targets, n_valid, perm, cell_start, table, B, N, nu, nv, p, q, method, (int)epochs, &tab_lds, &chunk);
+    FitMode mode = kFitLds;
+    int chunk = 0, block = 0;
+    const int rc = fit_common(a, L, targets, n_valid, perm, cell_start, table, B, N, nu, nv, p, q, method, (int)epochs, &mode, &chunk, &block);
     if (rc != ART_OK) return rc;
     if (B == 0) return ART_OK;
     if (!control_points || !exp_avg || !exp_avg_sq || !state_f64 || !state_i32 || !last_loss) return ART_EINVAL;
@@ -1078,8 +818,6 @@ extern "C" int art_surface_fit_run(float* control_points, float* exp_avg, float*
     a.patience = (int)patience; a.cooldown = (int)cooldown;
     a.factor = factor; a.threshold = threshold; a.min_lr = min_lr; a.sched_eps = scheduler_eps;
     const size_t lds = (size_t)L.total * sizeof(float);
-    if (chunk > 0) ART_FIT_DISPATCH_CHUNKED(surface_fit_run_chunked_kernel, fit_deg(p, q), B, fit_block(std::min<int64_t>(N, chunk)), lds, stream, a, L, chunk);
-    else ART_FIT_DISPATCH(surface_fit_run_kernel, fit_deg(p, q), tab_lds, B, fit_block(N), lds, stream, a, L);
-    ART_HIP(hipGetLastError());
-    return ART_OK;
+    ART_FIT_BY_DEGREE(fit_deg(p, q),
+                      return fit_launch(ART_FIT_BY_MODE(surface_fit_run_kernel, DEG, mode), B, block, lds, stream, a, L, chunk));
 }
