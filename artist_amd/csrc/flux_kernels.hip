@@ -910,6 +910,11 @@ static void launch_crop_bwd_tiled(hipStream_t stream, const float* dims, const f
                        grad_flux, grad_loss, (int)grad_loss_stride);
 }
 
+// flux_blur_kernels.hip: the blur mode of art_flux_crop_fwd.
+namespace art {
+int flux_blur_launch(const float* x, const float* covariance, int64_t B, int64_t Hh, int64_t W, float* out, hipStream_t stream);
+}
+
 static bool crop_args_ok(const void* a, const void* b, const void* c, const void* d, int64_t B, int64_t Hh, int64_t W)
 {
     return a && b && c && d && B >= 0 && Hh >= 1 && W >= 1 && Hh <= 65535 && Hh * W <= (int64_t)1 << 30 && B <= 65535;
@@ -926,6 +931,8 @@ extern "C" int art_flux_crop_fwd(const float* flux, const float* target_dims, in
                                  double crop_width, double crop_height, float* out, float* centers, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (crop_width == -1.0 && crop_height == -1.0)          // blur mode: centers holds the windows' covariances and is READ
+        return target_dims ? ART_EINVAL : flux_blur_launch(flux, centers, B, Hh, W, out, stream);
     if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, out, centers, B, Hh, W)) return ART_EINVAL;
     hipLaunchKernelGGL(flux_com_kernel<NormalisedWeights>, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, centers);

@@ -93,6 +93,52 @@ def crop_flux_distributions_around_center(flux_distributions: torch.Tensor, sola
     return FluxCrop.apply(flux_distributions, dims, crop_width, crop_height)
 
 
+class FluxBlur(torch.autograd.Function):
+    """``art_flux_crop_fwd`` in its blur mode (crop size (-1, -1), no target dimensions, the covariances where the crop writes
+    its centres).  The operator is its own adjoint: the backward pass is the same call on the upstream gradient."""
+
+    @staticmethod
+    def _launch(x: torch.Tensor, covariance: torch.Tensor) -> torch.Tensor:
+        B, Hh, W = x.shape
+        out = torch.empty_like(x)
+        _lib.call("art_flux_crop_fwd", x.device, x.data_ptr(), None, B, Hh, W, -1.0, -1.0, out.data_ptr(), covariance.data_ptr())
+        return out
+
+    @staticmethod
+    def forward(ctx, flux, covariance):
+        ctx.save_for_backward(covariance)
+        return FluxBlur._launch(flux, covariance)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (covariance,) = ctx.saved_tensors
+        return FluxBlur._launch(grad_out.contiguous(), covariance), None
+
+
+def blur_flux(flux: torch.Tensor, covariance: torch.Tensor) -> torch.Tensor:
+    """Each bitmap of ``flux [B,Hh,W]`` convolved with its own Gaussian window, ``covariance [B,3]`` =
+    ``(S_rr, S_rc, S_cc)`` in pixels^2 (r the bitmap's row, c its column), as ``[B,Hh,W]``: the convolved sun's second half
+    (the operator is defined in include/artist_hip.h at ``art_flux_crop_fwd`` and again, in fp64, in
+    tests/flux_blur_ref.py).  Differentiable w.r.t. ``flux`` - the window is symmetric about its centre and the bitmap is
+    zero-extended, so the gradient is the same blur of the upstream gradient, one launch, the same bits as a forward call on
+    it.  The covariance is a constant: one that requires grad is a ``ValueError``.  A covariance that is not finite, not
+    positive semi-definite or wider than the kernel's window (``4 sqrt(max(S_rr, S_cc)) > 64``) makes its bitmap NaN - marked
+    in the result, no host read.  fp32 on the GPU only; one launch and one allocation (the result): capturable."""
+    if covariance.requires_grad:
+        raise ValueError("the covariance of blur_flux is a constant (to first order the sun's image does not depend on the "
+                         "learned surface): detach it")
+    if flux.device.type != "cuda" or covariance.device.type != "cuda":
+        raise _lib.ArtistHipError(f"blur_flux runs on the GPU only (got tensors on {flux.device} and {covariance.device}); "
+                                  "there is no CPU fallback")
+    _require_cuda(flux, covariance)
+    if flux.dtype != torch.float32 or covariance.dtype != torch.float32:
+        raise ValueError(f"blur_flux takes float32 tensors, got {flux.dtype} and {covariance.dtype}")
+    if flux.dim() != 3 or tuple(covariance.shape) != (flux.shape[0], 3):
+        raise ValueError(f"flux must be [B,Hh,W] and the covariance [B,3], got {tuple(flux.shape)} and {tuple(covariance.shape)}")
+    return FluxBlur.apply(flux.contiguous(), covariance.contiguous())
+
+
 class _FluxLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prediction, ground_truth, kind):

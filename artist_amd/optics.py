@@ -14,13 +14,16 @@ An attenuation ``model`` is one of
 Mirror slope errors: :func:`tilt_normals` tilts surface normals by slope pairs before alignment,
 :func:`slope_sample` draws the standard-normal pairs of a group's heliostats, :func:`expand_over_samples` repeats per-heliostat
 rows over their activations with a fixed-order backward.
+
+The convolved sun: :func:`sun_image_covariance` is the covariance, in pixels^2, of the image that a Gaussian
+sun leaves on a planar target around each heliostat's chief ray - the window of ``artist_amd.flux.blur_flux``.
 """
 from __future__ import annotations
 
 import torch
 
 __all__ = ["slant_ranges", "atmospheric_transmittance", "heliostat_intensity_factors", "tilt_normals", "slope_sample",
-           "expand_over_samples", "SLOPE_ERROR_STREAM"]
+           "expand_over_samples", "SLOPE_ERROR_STREAM", "sun_image_covariance"]
 
 #: The stream of a mirror's slope-error sample is the sampler's with the seed XOR this (DESIGN.md 4.15): the 64-bit constant of
 #: the splitmix64 finaliser, non-zero and different from ``artist_amd.scene.OPTICAL_ERROR_STREAM``, so that the Philox keys
@@ -128,3 +131,53 @@ def heliostat_intensity_factors(heliostat_group, solar_tower, target_area_indice
     transmittance = atmospheric_transmittance(slant_ranges(positions, centres.to(positions.dtype)), model)
     reflectivity = getattr(heliostat_group, "active_reflectivities", None)
     return (1.0 - transmittance).clamp(0.0, 1.0), (0.935 if reflectivity is None else reflectivity)
+
+
+def sun_image_covariance(points: torch.Tensor, normals: torch.Tensor, incident: torch.Tensor, target_area_indices: torch.Tensor,
+                         centers: torch.Tensor, plane_normals: torch.Tensor, dimensions: torch.Tensor,
+                         angular_covariance: torch.Tensor, resolution) -> torch.Tensor:
+    """``[H,3]`` = ``(S_rr, S_rc, S_cc)`` in pixels^2 (r the bitmap's row, c its column): the covariance of the spot that a
+    Gaussian sun of ``angular_covariance`` - ``(C_uu, C_ue, C_ee)`` in rad^2, ``[3]`` or one row per heliostat ``[H,3]``, in the
+    ``(u, e)`` order of the distortions - leaves on the planar target of each heliostat, to first order in the tilt of the
+    reflected ray.
+
+    ``points``, ``normals [H,P,4]`` the aligned surfaces, ``incident [H,4]``, ``target_area_indices [H]`` into the PLANAR tables
+    ``centers``, ``plane_normals [T,4]`` and ``dimensions [T,2]`` (width, height), ``resolution`` = (columns, rows) of the bitmap,
+    the tracer's ``bitmap_resolution``.  Per heliostat: ``o`` the mean point, ``n`` the normalised mean normal,
+    ``d = i - 2 (i.n) n`` the chief ray, ``t = ((c - o).m) / (d.m)`` its range to the plane of normal ``m``.  A tilt ``(u, e)``
+    turns ``d`` by ``u a_u + e a_e`` with ``a_u = (-d_n, d_e, 0)`` and ``a_e = (0, -d_u, d_n)`` (the first-order term of the
+    reference's ``rotate_distortions``), which moves the hit point by ``t (a - d (a.m) / (d.m))``; with the bitmap's two flips
+    (row = top - U, column = right - E) that is ``J [2,2]`` and ``S = J C J^T``.
+
+    One ``J`` per heliostat: slant range and incidence vary by about a percent across a mirror.  Torch ops in fp64 on a few
+    values per heliostat, under ``no_grad``, on the arguments' device, no synchronisation; the result is fp32 and a constant
+    (to first order the image does not depend on the learned surface)."""
+    with torch.no_grad():
+        f64 = torch.float64
+        # (the sums run in fp64 inside the reduction: no fp64 copy of the surfaces)
+        o = points[..., :3].mean(dim=1, dtype=f64)
+        n = torch.nn.functional.normalize(normals[..., :3].mean(dim=1, dtype=f64), dim=-1)
+        i = incident[..., :3].to(f64)
+        d = i - 2.0 * (i * n).sum(-1, keepdim=True) * n
+        index = target_area_indices.long()
+        c = centers.index_select(0, index)[:, :3].to(f64)
+        m = plane_normals.index_select(0, index)[:, :3].to(f64)
+        size = dimensions.index_select(0, index).to(f64)
+        dm = (d * m).sum(-1, keepdim=True)
+        t = ((c - o) * m).sum(-1, keepdim=True) / dm
+        # the two tilt axes at once: a_u = z x d = (-d_n, d_e, 0) and a_e = x x d = (0, -d_u, d_n), as [H,2,3]
+        eye = torch.eye(3, dtype=f64, device=d.device)
+        axes = torch.stack((eye[2], eye[0])).unsqueeze(0).expand(d.shape[0], 2, 3)
+        d2, m2 = d.unsqueeze(1), m.unsqueeze(1)
+        a = torch.linalg.cross(axes, d2.expand(-1, 2, -1), dim=-1)
+        shift = t.unsqueeze(1) * (a - d2 * ((a * m2).sum(-1, keepdim=True) / dm.unsqueeze(1)))       # [H, (u, e), (E, N, U)]
+        per_metre = torch.stack(((float(resolution[1]) - 1.0) / size[:, 1], (float(resolution[0]) - 1.0) / size[:, 0]), dim=-1)
+        # J [H, (row, column), (u, e)]: row = top - U, column = right - E
+        J = -torch.stack((shift[..., 2], shift[..., 0]), dim=1) * per_metre.unsqueeze(-1)
+        C = angular_covariance.to(device=d.device, dtype=f64)
+        if C.shape not in ((3,), (d.shape[0], 3)):
+            raise ValueError(f"angular_covariance must be [3] or [{d.shape[0]},3] = (C_uu, C_ue, C_ee), got {tuple(C.shape)}")
+        C = torch.stack((C[..., 0], C[..., 1], C[..., 1], C[..., 2]), dim=-1).reshape(-1, 2, 2)      # [H or 1, (u, e), (u, e)]
+        JC = (J.unsqueeze(-1) * C.unsqueeze(1)).sum(dim=2)                                           # element-wise: no batched GEMM
+        S = (JC.unsqueeze(2) * J.unsqueeze(1)).sum(dim=-1)                                           # [H, (r, c), (r, c)]
+        return torch.stack((S[:, 0, 0], S[:, 0, 1], S[:, 1, 1]), dim=-1).to(torch.float32)

@@ -20,9 +20,10 @@ import logging
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, optics
 from ._memo import Memo
 from .blocking import create_blocking_primitives_rectangles_by_index, create_shading_primitives
+from .flux import blur_flux
 from .sampling import DistortionsDataset, RestrictedDistributedSampler
 
 log = logging.getLogger(__name__)
@@ -79,6 +80,15 @@ def _cylinder_tables(tower):
     return (c.centers, c.normals, c.axes, c.radii, c.heights, c.opening_angles)
 
 
+class _ChiefRayDataset:
+    """The distortions of a convolved sun (``Sun.integration == "convolved"``): one ray per point and no tilt, ``[rows,1,P]``
+    views of one interleaved buffer like a sample's.  Nothing is drawn."""
+
+    def __init__(self, number_of_rows: int, number_of_points: int, device) -> None:
+        both = torch.zeros((int(number_of_rows), 1, int(number_of_points), 2), dtype=torch.float32, device=device)
+        self.distortions_u, self.distortions_e = both[..., 0], both[..., 1]
+
+
 class HeliostatRayTracer:
     """See ``artist/raytracing/heliostat_ray_tracer.py:19-69`` for the attribute documentation.
 
@@ -86,7 +96,18 @@ class HeliostatRayTracer:
     neighbouring heliostat before it arrives, evaluated with the blocking mask against per-heliostat sheared copies of the
     neighbours' rectangles.  The third factor returned by ``trace_rays``, ``blocking_factor``, then counts the
     rays that are neither blocked nor shaded.  ``shading_active=True`` with ``blocking_active=False`` traces with shading
-    only: the rectangles are built, the blocking filter is skipped."""
+    only: the rectangles are built, the blocking filter is skipped.
+
+    A light source with ``integration == "convolved"`` (``artist_amd.scene.Sun``; read here, when the tracer is built;
+    DESIGN.md 4.16) is not sampled: every mirror point sends its one undistorted chief ray, carrying the power of the
+    ``number_of_rays`` rays it stands for, and each heliostat's bitmap is convolved with the Gaussian image of the sun on its
+    target (``optics.sun_image_covariance``, ``flux.blur_flux``) - the expectation of the sampled bitmap to first order,
+    without sampling noise, differentiable like it.  The sun's angular covariance is ``scale_tril scale_tril^T`` plus
+    ``sigma_h^2 I`` for a heliostat with an optical error (exact: both are Gaussian).  For a Gaussian sun centred on 0, planar
+    targets and constant optical errors (``ValueError`` otherwise), on the GPU.  Known limits: a chief ray that misses the target
+    contributes nothing, though part of its image would land on it; blocking and shading act on the chief rays; the window does
+    not depend on the learned surface and is not differentiated.  The three factors returned by the trace calls are those of
+    the chief rays."""
 
     #: publish ``heliostat_group.preferred_reflection_directions`` like the reference does (:285-290)
     publish_reflection_directions = True
@@ -112,7 +133,8 @@ class HeliostatRayTracer:
         )
         # A rank keeps the distortions of the heliostat samples it owns only (the reference samples all [H,R,P] on every
         # rank, sampling.py:49-53): 8 B per ray of this rank instead of 8 B per ray of the field.
-        self.distortions_dataset = DistortionsDataset(
+        self.integration = getattr(self.light_source, "integration", "sampled")
+        self.distortions_dataset = self._chief_rays(number_of_samples) if self.integration == "convolved" else DistortionsDataset(
             light_source=self.light_source,
             number_of_points_per_heliostat=self.heliostat_group.active_surface_points.shape[1],
             number_of_active_heliostats=number_of_samples,
@@ -159,6 +181,8 @@ class HeliostatRayTracer:
             self.ray_magnitude = power_single_heliostat / rays_per_heliostat
         else:
             self.ray_magnitude = 1.0
+        # a chief ray carries what the rays of its point carry together: the bitmap is the expectation of the sampled one
+        self._rays_per_traced_ray = int(self.light_source.number_of_rays) if self.integration == "convolved" else 1
         self._local_cache = None
         # what a trace call learns from its arguments by a host read: once per tensor object and version (artist_amd/_memo.py),
         # so index tensors and masks are changed with tracked in-place ops, or replaced
@@ -168,6 +192,51 @@ class HeliostatRayTracer:
         self._scatter_angle = Memo("the largest scatter angle of the distortions")
 
     # ------------------------------------------------------------------------------------------
+    def _chief_rays(self, number_of_samples: int) -> _ChiefRayDataset:
+        """The checks of a convolved sun, and its zero distortions for the rows this rank owns."""
+        sun = self.light_source
+        dist = getattr(sun, "distribution", None)
+        if not isinstance(dist, torch.distributions.MultivariateNormal):
+            raise ValueError("integration='convolved' needs a Gaussian sun (distribution_type 'normal'): the image of a radial sun "
+                             "shape (pillbox, Buie, tabulated) is not a Gaussian window")
+        loc, _ = sun._host_law()
+        if loc[0] != 0.0 or loc[1] != 0.0:
+            raise ValueError(f"integration='convolved' needs a sun centred on 0 (the chief ray is the undistorted one), got loc {loc}")
+        errors = getattr(self.heliostat_group, "active_optical_errors", None)
+        if errors is not None:
+            if not isinstance(errors, torch.Tensor) or tuple(errors.shape) != (number_of_samples,):
+                raise ValueError(f"optical_errors must be a tensor with one sigma per active heliostat, shape [{number_of_samples}]; "
+                                 f"got {tuple(getattr(errors, 'shape', ()))}")
+            if errors.requires_grad:
+                raise ValueError("integration='convolved' takes the optical errors as constants (the window is not differentiated): "
+                                 "optical_errors.requires_grad must be False")
+        if dist.loc.device.type != "cuda":
+            raise _lib.ArtistHipError(f"integration='convolved' runs on the GPU only (the light source is on {dist.loc.device}); "
+                                      "there is no CPU fallback")
+        with torch.no_grad():       # C = L L^T of the sun's scale_tril, element by element: (C_uu, C_ue, C_ee)
+            tril = dist.scale_tril.float()
+            self._sun_covariance = torch.stack((tril[0, 0] * tril[0, 0], tril[0, 0] * tril[1, 0],
+                                                tril[1, 0] * tril[1, 0] + tril[1, 1] * tril[1, 1]))
+        rows = len(self.distortions_sampler.rank_indices) if self.world_size > 1 else number_of_samples
+        return _ChiefRayDataset(rows, self.heliostat_group.active_surface_points.shape[1], dist.loc.device)
+
+    def _angular_covariance(self, idx) -> torch.Tensor:
+        """``(C_uu, C_ue, C_ee)`` of the sun (formed when the tracer was built), ``[3]``, or ``[rows,3]`` with the optical errors
+        of this rank's rows as the group holds them now: device ops."""
+        with torch.no_grad():
+            C = self._sun_covariance
+            errors = getattr(self.heliostat_group, "active_optical_errors", None)
+            if errors is None:
+                return C
+            if errors.requires_grad:        # (every activation rebinds the group's tensor: what was checked at construction is gone)
+                raise ValueError("integration='convolved' takes the optical errors as constants: optical_errors.requires_grad "
+                                 "must be False")
+            errors = errors.detach().float().to(C.device)
+            if idx is not None:
+                errors = errors.index_select(0, idx)
+            variance = errors * errors       # (no host constant: this runs inside a captured epoch)
+            return torch.stack((C[0] + variance, C[1].expand_as(variance), C[2] + variance), dim=1)
+
     def get_sampler_indices(self) -> torch.Tensor:
         """Indices of the heliostat samples assigned to this rank (:205-218)."""
         return torch.tensor(self.distortions_sampler.rank_indices, device=self.distortions_dataset.distortions_u.device)
@@ -212,6 +281,7 @@ class HeliostatRayTracer:
 
         tower = self.scenario.solar_tower
         self._validate_targets(target_area_indices, tower)
+        convolved = self.integration == "convolved"
         # a float goes to the kernel as before; a tensor [H] is applied to the traced bitmaps (ops.scale_heliostat_rows)
         ray_extinction_factor, mirror_reflectivity, extinction_rows, reflectivity_rows = ops.split_intensity_factors(
             ray_extinction_factor, mirror_reflectivity, int(group.number_of_active_heliostats), points.device, self._checked_factors)
@@ -235,16 +305,21 @@ class HeliostatRayTracer:
                        bool(self.blocking_active))
         flux, factors, flags = ops.TraceRays.apply(
             points, normals, incident_ray_directions, dist_u, dist_e, target_area_indices, *_planar_tables(tower, points.device),
-            float(self.ray_magnitude), float(ray_extinction_factor), float(mirror_reflectivity), width, height,
-            bool(per_target) and not scaled,
+            float(self.ray_magnitude) * self._rays_per_traced_ray, float(ray_extinction_factor), float(mirror_reflectivity),
+            width, height, bool(per_target) and not scaled and not convolved,
             _cylinder_tables(tower), *(rectangles or (None, None, None, None, -1.0, True)),
             self._points_per_facet(points), *shading)
         if self.blocking_active:
             self._filter_flags, self._filtered = flags, None       # (indices on demand: nonzero() waits for the device)
+        if convolved:           # the sun's image on each heliostat's target (a new tensor: ops.bitmap_moments has nothing for it)
+            flux = blur_flux(flux, optics.sun_image_covariance(
+                points, normals, incident_ray_directions, target_area_indices, *_planar_tables(tower, points.device),
+                self._angular_covariance(idx), (width, height)))
         if scaled:
             flux, factors = ops.scale_heliostat_rows(flux, factors, extinction_rows, reflectivity_rows)
-            if per_target:      # (the fused per-target mode sums inside the kernel: trace per heliostat, scale, then sum)
-                flux = ops.per_target_sum(flux, target_area_indices, sum(target_area_counts(tower)))
+        if per_target and (scaled or convolved):
+            # (the fused per-target mode sums inside the kernel: trace per heliostat, scale or blur, then sum)
+            flux = ops.per_target_sum(flux, target_area_indices, sum(target_area_counts(tower)))
         return flux, factors[0], factors[1], factors[2]
 
     def trace_rays(self, incident_ray_directions: torch.Tensor, active_heliostats_mask: torch.Tensor,
@@ -306,6 +381,9 @@ class HeliostatRayTracer:
             lo, hi = int(target_area_indices.min()), int(target_area_indices.max())
             if lo < 0 or hi >= sum(target_area_counts(tower)):
                 raise IndexError("target_area_indices out of range")
+            if self.integration == "convolved" and hi >= target_area_counts(tower)[0]:
+                raise ValueError("integration='convolved' traces planar target areas only (the sun's image on a cylinder is not "
+                                 "one Gaussian window per bitmap); target_area_indices name a cylindrical area")
             return True
         if target_area_indices.numel() > 0:
             self._checked_targets.lookup(target_area_indices, check)

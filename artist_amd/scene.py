@@ -27,6 +27,10 @@ from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nu
 #: with a per-sun sample cache).
 SAMPLERS = ("torch", "hip")
 
+#: How a tracer integrates over the sun shape (:attr:`Sun.integration`): ``"sampled"`` (the default: ``number_of_rays`` draws
+#: per mirror point) or ``"convolved"`` (one undistorted ray per point and a Gaussian window per bitmap).
+INTEGRATIONS = ("sampled", "convolved")
+
 #: ``distribution_type`` values of :class:`Sun` next to ``"normal"``: radially symmetric shapes, each held as a quantile table.
 RADIAL_TYPES = ("pillbox", "buie", "tabulated")
 SOLAR_DISC_HALF_ANGLE = 4.65e-3         # rad: the edge of the solar disc
@@ -187,7 +191,13 @@ class Sun:
     ``sampler`` chooses how a GPU-resident sun draws (``SAMPLERS``); it may be set on a light source that is already
     loaded.  With ``"hip"`` the last sample is kept (one per sun) and handed out again, without a launch or a
     synchronisation, to every draw with the same (seed, rows, number of rays and points, device, law): the views it
-    returns are SHARED between those callers and must not be written (a write is noticed and makes the next draw anew)."""
+    returns are SHARED between those callers and must not be written (a write is noticed and makes the next draw anew).
+
+    ``integration`` (``INTEGRATIONS``) says how a ``HeliostatRayTracer`` built on this sun integrates over the
+    sun shape: ``"sampled"`` (the default) traces ``number_of_rays`` draws per mirror point; ``"convolved"`` traces the chief ray
+    of every point and convolves each bitmap with the Gaussian image of the sun - the expectation of the sampled bitmap to
+    first order, without its noise.  Like ``sampler`` it is set on the light source, before the tracers are built, so the tracers
+    that the reconstructors and ``AimPointOptimizer`` build pick it up; it changes nothing about what the sun draws."""
 
     def __init__(self, number_of_rays: int, distribution_parameters: dict | None = None,
                  device: torch.device | None = None, sampler: str = "torch") -> None:
@@ -213,6 +223,17 @@ class Sun:
         self._cache_errors = None   # the last "hip" draw with optical errors (see _hip_rows_with_errors)
         self._sampler = None
         self.sampler = sampler
+        self._integration = "sampled"
+
+    @property
+    def integration(self) -> str:
+        return self._integration
+
+    @integration.setter
+    def integration(self, name: str) -> None:
+        if name not in INTEGRATIONS:
+            raise ValueError(f"Unknown sun integration {name!r}; expected one of {INTEGRATIONS}.")
+        self._integration = name
 
     @property
     def sampler(self) -> str:

@@ -334,6 +334,27 @@ int art_align_bwd(const float *points, const float *normals, const float *orient
  *   the two centre coordinates and chained through x centre = sum(x flux) / (sum flux + 1e-8), :165-182).
  *   centers [B,3] as written by the forward call; grad_out [B,Hh,W]; grad_flux [B,Hh,W] out (fully written);
  *   workspace: at least 2 * B floats of device memory (per bitmap the gradients of the two centre coordinates).
+ *
+ * BLUR MODE of art_flux_crop_fwd (the convolved sun): crop_width == -1.0 && crop_height == -1.0 (any other non-positive pair
+ * is the crop, as before).  Each bitmap is convolved with a Gaussian window of its own:
+ *   target_dims must be NULL; centers [B,3] is READ: (S_rr, S_rc, S_cc), the window's covariance in pixels^2, r the bitmap's
+ *   row and c its column; flux [B,Hh,W] in, out [B,Hh,W] fully written; out must not overlap flux (ART_EINVAL).
+ *   B == 0, Hh == 0 or W == 0: ART_OK, nothing launched.  A null pointer, a non-NULL target_dims, B or Hh > 65535 or
+ *   Hh * W > 2^30: ART_EINVAL before any launch.
+ *   Definition.  tap(v): the integers k = -K..K, K = ceil(4 sqrt(v)), with weights exp(-k^2 / (2 v)) over their sum; the one
+ *   tap k = 0 of weight 1 when v < 1e-4.
+ *     column pass       a = S_cc - S_rc^2 / S_rr,  y[r,c] = sum_k tap(a)[k] x[r, c - k]
+ *     sheared row pass  s = S_rc / S_rr,           z[r,c] = sum_k tap(S_rr)[k] lerp(y[r - k, .], c - s k)
+ *   lerp interpolates linearly between the two neighbouring columns; S_rr < 1e-4: the row pass is the identity and a = S_cc.
+ *   x is zero outside the image, y is kept on the extended domain (its values beyond the image's edges enter the row pass) and
+ *   z is cut to the image: zero-extension, a convolution with a point-symmetric stencil, restriction.  The operator is
+ *   therefore ITS OWN ADJOINT: its backward pass is the same call on the upstream gradient (there is no _bwd entry point).
+ *   One kernel, both passes out of LDS (one read and one write of the bitmaps), no atomics, taps summed in ascending k in fp32
+ *   (weights and shear formed in fp64); a bitmap's bits depend neither on B, nor on its place in the batch, nor on the run.
+ *   LIMIT: both passes hold at most 129 taps: every covariance with 4 sqrt(max(S_rr, S_cc)) <= 64, i.e. S_rr, S_cc <= 256, is
+ *   supported at every image size and shear (a steeper window only adds tile columns to walk).  A covariance beyond that,
+ *   one that is not finite, or one that is not positive semi-definite (S_rr < 0, S_cc < 0 or S_rc^2 > S_rr S_cc (1 + 1e-5))
+ *   makes ITS bitmap NaN - marked in the result itself, no host read, no status word; the other bitmaps keep their bits.
  * ------------------------------------------------------------------------------------------- */
 int art_flux_crop_fwd(const float *flux, const float *target_dims, int64_t B, int64_t Hh, int64_t W,
                       double crop_width, double crop_height, float *out, float *centers, void *stream);
