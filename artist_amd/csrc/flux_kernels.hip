@@ -913,6 +913,9 @@ static void launch_crop_bwd_tiled(hipStream_t stream, const float* dims, const f
 // flux_blur_kernels.hip: the blur mode of art_flux_crop_fwd.
 namespace art {
 int flux_blur_launch(const float* x, const float* covariance, int64_t B, int64_t Hh, int64_t W, float* out, hipStream_t stream);
+// radial_blur_kernels.hip: its radial window mode.
+int flux_radial_blur_launch(const float* x, const float* metric, const float* table, int64_t K, int64_t B, int64_t Hh, int64_t W,
+                            float* out, hipStream_t stream);
 }
 
 static bool crop_args_ok(const void* a, const void* b, const void* c, const void* d, int64_t B, int64_t Hh, int64_t W)
@@ -933,6 +936,11 @@ extern "C" int art_flux_crop_fwd(const float* flux, const float* target_dims, in
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (crop_width == -1.0 && crop_height == -1.0)          // blur mode: centers holds the windows' covariances and is READ
         return target_dims ? ART_EINVAL : flux_blur_launch(flux, centers, B, Hh, W, out, stream);
+    if (crop_width == -2.0) {       // radial window mode: crop_height = -K, target_dims holds the quantile table, centers the metrics; both READ
+        const double K = -crop_height;
+        if (!(K >= 1.0 && K <= 4096.0) || K != floor(K)) return ART_EINVAL;
+        return flux_radial_blur_launch(flux, centers, target_dims, (int64_t)K, B, Hh, W, out, stream);
+    }
     if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, out, centers, B, Hh, W)) return ART_EINVAL;
     hipLaunchKernelGGL(flux_com_kernel<NormalisedWeights>, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, (int)Hh, (int)W, centers);

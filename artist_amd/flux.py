@@ -139,6 +139,61 @@ def blur_flux(flux: torch.Tensor, covariance: torch.Tensor) -> torch.Tensor:
     return FluxBlur.apply(flux.contiguous(), covariance.contiguous())
 
 
+class RadialFluxBlur(torch.autograd.Function):
+    """``art_flux_crop_fwd`` in its radial window mode (crop size (-2, -K), the quantile table where the crop reads the target
+    dimensions, the metrics where it writes its centres).  The operator is its own adjoint: the backward pass is the same call
+    on the upstream gradient."""
+
+    @staticmethod
+    def _launch(x: torch.Tensor, metric: torch.Tensor, quantile_table: torch.Tensor) -> torch.Tensor:
+        B, Hh, W = x.shape
+        out = torch.empty_like(x)
+        _lib.call("art_flux_crop_fwd", x.device, x.data_ptr(), quantile_table.data_ptr(), B, Hh, W, -2.0,
+                  -float(quantile_table.shape[0] - 1), out.data_ptr(), metric.data_ptr())
+        return out
+
+    @staticmethod
+    def forward(ctx, flux, metric, quantile_table):
+        ctx.save_for_backward(metric, quantile_table)
+        return RadialFluxBlur._launch(flux, metric, quantile_table)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        metric, quantile_table = ctx.saved_tensors
+        return RadialFluxBlur._launch(grad_out.contiguous(), metric, quantile_table), None, None
+
+
+def radial_blur_flux(flux: torch.Tensor, metric: torch.Tensor, quantile_table: torch.Tensor) -> torch.Tensor:
+    """Each bitmap of ``flux [B,Hh,W]`` convolved with the image of a radial sun shape on its target, as ``[B,Hh,W]``: ``metric
+    [B,3]`` = ``(M_rr, M_rc, M_cc)`` in pixels^2/rad^2 (``optics.sun_image_covariance`` of the unit angular covariance
+    ``(1, 0, 1)``), ``quantile_table [K+1]`` the sun's table in rad^2 (``scene.radial_quantile_table``), ``1 <= K <= 4096``.  The
+    window is the table's density on the ellipses ``(dr, dc) M^-1 (dr, dc)^T = theta^2``, averaged over 4 x 4 sub-pixel points,
+    cut at the largest node whose ellipse fits 64 pixels - what lies beyond is dropped, ``optics.radial_window_kept_fraction``
+    says how much stays (the operator is defined in include/artist_hip.h at ``art_flux_crop_fwd`` and again,
+    in fp64, in tests/radial_blur_ref.py).  Differentiable w.r.t. ``flux`` - the stencil is point-symmetric and the bitmap is
+    zero-extended, so the gradient is the same call on the upstream gradient, one launch, the same bits as a forward call on
+    it.  Metric and table are constants: one that requires grad is a ``ValueError``.  A metric that is not finite, not positive
+    definite, or so wide that not even the table's first annulus fits makes its bitmap NaN, a table that is not finite or
+    decreases makes every bitmap NaN - marked in the result, no host read.  fp32 on the GPU only; one launch and one allocation
+    (the result): capturable."""
+    if metric.requires_grad or quantile_table.requires_grad:
+        raise ValueError("the metric and the quantile table of radial_blur_flux are constants (to first order the sun's image does "
+                         "not depend on the learned surface): detach them")
+    if flux.dtype != torch.float32 or metric.dtype != torch.float32 or quantile_table.dtype != torch.float32:
+        raise ValueError(f"radial_blur_flux takes float32 tensors, got {flux.dtype}, {metric.dtype} and {quantile_table.dtype}")
+    if flux.dim() != 3 or tuple(metric.shape) != (flux.shape[0], 3) or quantile_table.dim() != 1 or \
+            not 2 <= quantile_table.shape[0] <= 4097:
+        raise ValueError(f"flux must be [B,Hh,W], the metric [B,3] and the quantile table [K+1] with 1 <= K <= 4096, got "
+                         f"{tuple(flux.shape)}, {tuple(metric.shape)} and {tuple(quantile_table.shape)}")
+    devices = (flux.device, metric.device, quantile_table.device)
+    if any(d.type != "cuda" for d in devices):
+        raise _lib.ArtistHipError(f"radial_blur_flux runs on the GPU only (got tensors on {devices[0]}, {devices[1]} and "
+                                  f"{devices[2]}); there is no CPU fallback")
+    _require_cuda(flux, metric, quantile_table)
+    return RadialFluxBlur.apply(flux.contiguous(), metric.contiguous(), quantile_table.contiguous())
+
+
 class _FluxLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prediction, ground_truth, kind):

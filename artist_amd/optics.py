@@ -16,14 +16,17 @@ Mirror slope errors: :func:`tilt_normals` tilts surface normals
 rows over their activations with a fixed-order backward.
 
 The convolved sun: :func:`sun_image_covariance` is the covariance, in pixels^2, of the image that a Gaussian
-sun leaves on a planar target around each heliostat's chief ray - the window of ``artist_amd.flux.blur_flux``.
+sun leaves on a planar target around each heliostat's chief ray - the window of ``artist_amd.flux.blur_flux``.  With the unit
+angular covariance ``(1, 0, 1)`` it is the metric ``M = J J^T`` of a radial sun's image, the window of
+``artist_amd.flux.radial_blur_flux``; :func:`radial_window_kept_fraction` says how much of such a sun its 64-pixel stencil keeps.
 """
 from __future__ import annotations
 
 import torch
 
 __all__ = ["slant_ranges", "atmospheric_transmittance", "heliostat_intensity_factors", "tilt_normals", "slope_sample",
-           "expand_over_samples", "SLOPE_ERROR_STREAM", "sun_image_covariance"]
+           "expand_over_samples", "SLOPE_ERROR_STREAM", "sun_image_covariance", "radial_window_kept_fraction",
+           "RADIAL_WINDOW_RADIUS"]
 
 #: The stream of a mirror's slope-error sample is the sampler's with the seed XOR this (DESIGN.md 4.15): the 64-bit constant of
 #: the splitmix64 finaliser, non-zero and different from ``artist_amd.scene.OPTICAL_ERROR_STREAM``, so that the Philox keys
@@ -181,3 +184,34 @@ def sun_image_covariance(points: torch.Tensor, normals: torch.Tensor, incident: 
         JC = (J.unsqueeze(-1) * C.unsqueeze(1)).sum(dim=2)                                           # element-wise: no batched GEMM
         S = (JC.unsqueeze(2) * J.unsqueeze(1)).sum(dim=-1)                                           # [H, (r, c), (r, c)]
         return torch.stack((S[:, 0, 0], S[:, 0, 1], S[:, 1, 1]), dim=-1).to(torch.float32)
+
+
+#: the radial window's stencil reaches 64 pixels from its centre, in rows and in columns (the Gaussian blur's own limit)
+RADIAL_WINDOW_RADIUS = 64
+
+
+def radial_window_kept_fraction(metric: torch.Tensor, quantile_table: torch.Tensor) -> torch.Tensor:
+    """``[B]`` (fp64): the share ``k* / K`` of a radial sun's energy that ``flux.radial_blur_flux`` deposits for each ``metric
+    [B,3]`` = ``(M_rr, M_rc, M_cc)`` in pixels^2/rad^2 and the sun's ``quantile_table [K+1]`` in rad^2.  Node
+    ``k`` of the table is the ellipse of half extents ``sqrt(t2[k] M_rr)`` rows and ``sqrt(t2[k] M_cc)`` columns; ``k*`` is the
+    largest node whose two half extents are both at most 64 pixels, and the annuli beyond it are dropped.  NaN where the kernel
+    writes NaN: a metric that is not finite, has ``M_rr <= 0`` or ``M_cc <= 0`` or ``det <= 1e-6 M_rr M_cc``, ``k* = 0`` (not even
+    the first annulus fits), and everywhere for a table that is not finite, starts below 0 or decreases.  The rule of the
+    kernel in torch ops: fp64 from the arguments' fp32 values (so ``t2[k] M`` is exact), on the metric's device, no host read."""
+    if metric.dim() != 2 or metric.shape[1] != 3 or quantile_table.dim() != 1 or quantile_table.shape[0] < 2:
+        raise ValueError(f"the metric must be [B,3] and the quantile table [K+1] with K >= 1, got {tuple(metric.shape)} and "
+                         f"{tuple(quantile_table.shape)}")
+    with torch.no_grad():
+        f64 = torch.float64
+        M = metric.to(f64)
+        t2 = quantile_table.to(device=M.device, dtype=f64)
+        K = t2.shape[0] - 1
+        m_rr, m_rc, m_cc = M[:, 0], M[:, 1], M[:, 2]
+        det = m_rr * m_cc - m_rc * m_rc
+        metric_ok = torch.isfinite(M).all(dim=1) & (m_rr > 0) & (m_cc > 0) & (det > 1e-6 * (m_rr * m_cc))
+        table_ok = torch.isfinite(t2).all() & (t2[0] >= 0) & (t2[1:] >= t2[:-1]).all()
+        limit = float(RADIAL_WINDOW_RADIUS * RADIAL_WINDOW_RADIUS)
+        fits = (t2.unsqueeze(0) * m_rr.unsqueeze(1) <= limit) & (t2.unsqueeze(0) * m_cc.unsqueeze(1) <= limit)
+        k_star = fits.sum(dim=1) - 1                    # (the table does not decrease: the nodes that fit are a prefix)
+        kept = k_star.to(f64) / K
+        return torch.where(metric_ok & table_ok & (k_star >= 1), kept, torch.full_like(kept, float("nan")))

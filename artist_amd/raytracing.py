@@ -23,7 +23,7 @@ import torch
 from . import _lib, ops, optics
 from ._memo import Memo
 from .blocking import create_blocking_primitives_rectangles_by_index, create_shading_primitives
-from .flux import blur_flux
+from .flux import blur_flux, radial_blur_flux
 from .sampling import DistortionsDataset, RestrictedDistributedSampler
 
 log = logging.getLogger(__name__)
@@ -107,7 +107,13 @@ class HeliostatRayTracer:
     targets and constant optical errors (``ValueError`` otherwise), on the GPU.  Known limits: a chief ray that misses the target
     contributes nothing, though part of its image would land on it; blocking and shading act on the chief rays; the window does
     not depend on the learned surface and is not differentiated.  The three factors returned by the trace calls are those of
-    the chief rays."""
+    the chief rays.
+
+    A radial sun (pillbox, Buie, tabulated) is convolved when its ``window == "shape"`` (read with ``integration``; DESIGN.md
+    4.17): the window is then the sun's quantile table on the ellipses of the metric ``M = J J^T``
+    (``sun_image_covariance`` of the unit covariance, ``flux.radial_blur_flux``), and a heliostat's optical error is a Gaussian
+    blur of covariance ``sigma_h^2 M`` on top of it.  Annuli whose ellipse is wider than 64 pixels are dropped, not deposited
+    (``optics.radial_window_kept_fraction``); the other conditions and limits are those above."""
 
     #: publish ``heliostat_group.preferred_reflection_directions`` like the reference does (:285-290)
     publish_reflection_directions = True
@@ -134,6 +140,7 @@ class HeliostatRayTracer:
         # A rank keeps the distortions of the heliostat samples it owns only (the reference samples all [H,R,P] on every
         # rank, sampling.py:49-53): 8 B per ray of this rank instead of 8 B per ray of the field.
         self.integration = getattr(self.light_source, "integration", "sampled")
+        self._radial_window = False     # (set by the checks of a convolved sun)
         self.distortions_dataset = self._chief_rays(number_of_samples) if self.integration == "convolved" else DistortionsDataset(
             light_source=self.light_source,
             number_of_points_per_heliostat=self.heliostat_group.active_surface_points.shape[1],
@@ -194,11 +201,15 @@ class HeliostatRayTracer:
     # ------------------------------------------------------------------------------------------
     def _chief_rays(self, number_of_samples: int) -> _ChiefRayDataset:
         """The checks of a convolved sun, and its zero distortions for the rows this rank owns."""
+        from .scene import RadialSunShape
         sun = self.light_source
         dist = getattr(sun, "distribution", None)
-        if not isinstance(dist, torch.distributions.MultivariateNormal):
+        # the window of a radial sun: its own image (Sun.window = "shape", DESIGN.md 4.17); a normal sun's is the Gaussian either way
+        self._radial_window = isinstance(dist, RadialSunShape) and getattr(sun, "window", "gaussian") == "shape"
+        if not self._radial_window and not isinstance(dist, torch.distributions.MultivariateNormal):
             raise ValueError("integration='convolved' needs a Gaussian sun (distribution_type 'normal'): the image of a radial sun "
-                             "shape (pillbox, Buie, tabulated) is not a Gaussian window")
+                             "shape (pillbox, Buie, tabulated) is not a Gaussian window; set the sun's window = 'shape' to convolve "
+                             "with the shape's own image")
         loc, _ = sun._host_law()
         if loc[0] != 0.0 or loc[1] != 0.0:
             raise ValueError(f"integration='convolved' needs a sun centred on 0 (the chief ray is the undistorted one), got loc {loc}")
@@ -213,10 +224,13 @@ class HeliostatRayTracer:
         if dist.loc.device.type != "cuda":
             raise _lib.ArtistHipError(f"integration='convolved' runs on the GPU only (the light source is on {dist.loc.device}); "
                                       "there is no CPU fallback")
-        with torch.no_grad():       # C = L L^T of the sun's scale_tril, element by element: (C_uu, C_ue, C_ee)
-            tril = dist.scale_tril.float()
-            self._sun_covariance = torch.stack((tril[0, 0] * tril[0, 0], tril[0, 0] * tril[1, 0],
-                                                tril[1, 0] * tril[1, 0] + tril[1, 1] * tril[1, 1]))
+        with torch.no_grad():
+            if self._radial_window:     # the unit covariance, whose image is the metric M = J J^T
+                self._sun_covariance = torch.tensor([1.0, 0.0, 1.0], device=dist.loc.device)
+            else:                     # C = L L^T of the sun's scale_tril, element by element: (C_uu, C_ue, C_ee)
+                tril = dist.scale_tril.float()
+                self._sun_covariance = torch.stack((tril[0, 0] * tril[0, 0], tril[0, 0] * tril[1, 0],
+                                                    tril[1, 0] * tril[1, 0] + tril[1, 1] * tril[1, 1]))
         rows = len(self.distortions_sampler.rank_indices) if self.world_size > 1 else number_of_samples
         return _ChiefRayDataset(rows, self.heliostat_group.active_surface_points.shape[1], dist.loc.device)
 
@@ -225,17 +239,24 @@ class HeliostatRayTracer:
         of this rank's rows as the group holds them now: device ops."""
         with torch.no_grad():
             C = self._sun_covariance
+            variance = self._optical_error_variance(idx)
+            if variance is None:
+                return C
+            return torch.stack((C[0] + variance, C[1].expand_as(variance), C[2] + variance), dim=1)
+
+    def _optical_error_variance(self, idx):
+        """``sigma_h^2 [rows]`` of this rank's rows as the group holds the optical errors now (None: the group has none): device ops."""
+        with torch.no_grad():
             errors = getattr(self.heliostat_group, "active_optical_errors", None)
             if errors is None:
-                return C
+                return None
             if errors.requires_grad:        # (every activation rebinds the group's tensor: what was checked at construction is gone)
                 raise ValueError("integration='convolved' takes the optical errors as constants: optical_errors.requires_grad "
                                  "must be False")
-            errors = errors.detach().float().to(C.device)
+            errors = errors.detach().float().to(self._sun_covariance.device)
             if idx is not None:
                 errors = errors.index_select(0, idx)
-            variance = errors * errors       # (no host constant: this runs inside a captured epoch)
-            return torch.stack((C[0] + variance, C[1].expand_as(variance), C[2] + variance), dim=1)
+            return errors * errors           # (no host constant: this runs inside a captured epoch)
 
     def get_sampler_indices(self) -> torch.Tensor:
         """Indices of the heliostat samples assigned to this rank (:205-218)."""
@@ -311,7 +332,17 @@ class HeliostatRayTracer:
             self._points_per_facet(points), *shading)
         if self.blocking_active:
             self._filter_flags, self._filtered = flags, None       # (indices on demand: nonzero() waits for the device)
-        if convolved:           # the sun's image on each heliostat's target (a new tensor: ops.bitmap_moments has nothing for it)
+        if convolved and self._radial_window:
+            # a radial sun's own image: its table on the ellipses of M = J J^T; a heliostat's optical error, a Gaussian of
+            # covariance sigma_h^2 M in pixels, is convolved on top (sigma_h = 0 is the blur's identity)
+            metric = optics.sun_image_covariance(
+                points, normals, incident_ray_directions, target_area_indices, *_planar_tables(tower, points.device),
+                self._sun_covariance, (width, height))
+            flux = radial_blur_flux(flux, metric, self.light_source.distribution.quantile_table)
+            variance = self._optical_error_variance(idx)
+            if variance is not None:
+                flux = blur_flux(flux, metric * variance.unsqueeze(1))
+        elif convolved:         # the sun's image on each heliostat's target (a new tensor: ops.bitmap_moments has nothing for it)
             flux = blur_flux(flux, optics.sun_image_covariance(
                 points, normals, incident_ray_directions, target_area_indices, *_planar_tables(tower, points.device),
                 self._angular_covariance(idx), (width, height)))

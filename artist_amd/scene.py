@@ -31,6 +31,10 @@ SAMPLERS = ("torch", "hip")
 #: per mirror point) or ``"convolved"`` (one undistorted ray per point and a Gaussian window per bitmap).
 INTEGRATIONS = ("sampled", "convolved")
 
+#: The window of a convolved sun (:attr:`Sun.window`): ``"gaussian"`` (the default: Gaussian suns only) or ``"shape"`` (a radial
+#: sun's own image - its quantile table on the ellipses of the heliostat's metric; a normal sun keeps the Gaussian).
+WINDOWS = ("gaussian", "shape")
+
 #: ``distribution_type`` values of :class:`Sun` next to ``"normal"``: radially symmetric shapes, each held as a quantile table.
 RADIAL_TYPES = ("pillbox", "buie", "tabulated")
 SOLAR_DISC_HALF_ANGLE = 4.65e-3         # rad: the edge of the solar disc
@@ -197,7 +201,12 @@ class Sun:
     sun shape: ``"sampled"`` (the default) traces ``number_of_rays`` draws per mirror point; ``"convolved"`` traces the chief ray
     of every point and convolves each bitmap with the Gaussian image of the sun - the expectation of the sampled bitmap to
     first order, without its noise.  Like ``sampler`` it is set on the light source, before the tracers are built, so the tracers
-    that the reconstructors and ``AimPointOptimizer`` build pick it up; it changes nothing about what the sun draws."""
+    that the reconstructors and ``AimPointOptimizer`` build pick it up; it changes nothing about what the sun draws.
+
+    ``window`` (``WINDOWS``) is the convolved sun's window, read with ``integration`` when a tracer is built:
+    ``"gaussian"`` (the default) serves Gaussian suns only; with ``"shape"`` a radial sun is convolved with its own image - the
+    quantile table on the ellipses of each heliostat's metric (``flux.radial_blur_flux``), annuli wider than 64 pixels dropped
+    (``optics.radial_window_kept_fraction``) - and a normal sun takes the Gaussian window as before."""
 
     def __init__(self, number_of_rays: int, distribution_parameters: dict | None = None,
                  device: torch.device | None = None, sampler: str = "torch") -> None:
@@ -224,6 +233,7 @@ class Sun:
         self._sampler = None
         self.sampler = sampler
         self._integration = "sampled"
+        self._window = "gaussian"
 
     @property
     def integration(self) -> str:
@@ -234,6 +244,16 @@ class Sun:
         if name not in INTEGRATIONS:
             raise ValueError(f"Unknown sun integration {name!r}; expected one of {INTEGRATIONS}.")
         self._integration = name
+
+    @property
+    def window(self) -> str:
+        return self._window
+
+    @window.setter
+    def window(self, name: str) -> None:
+        if name not in WINDOWS:
+            raise ValueError(f"Unknown sun window {name!r}; expected one of {WINDOWS}.")
+        self._window = name
 
     @property
     def sampler(self) -> str:

@@ -335,8 +335,9 @@ int art_align_bwd(const float *points, const float *normals, const float *orient
  *   centers [B,3] as written by the forward call; grad_out [B,Hh,W]; grad_flux [B,Hh,W] out (fully written);
  *   workspace: at least 2 * B floats of device memory (per bitmap the gradients of the two centre coordinates).
  *
- * BLUR MODE of art_flux_crop_fwd (the convolved sun): crop_width == -1.0 && crop_height == -1.0 (any other non-positive pair
- * is the crop, as before).  Each bitmap is convolved with a Gaussian window of its own:
+ * BLUR MODE of art_flux_crop_fwd (the convolved sun): crop_width == -1.0 && crop_height == -1.0 (crop_width == -2.0 is the
+ * radial window mode below; any other non-positive pair is the crop, as before).  Each bitmap is convolved with a Gaussian
+ * window of its own:
  *   target_dims must be NULL; centers [B,3] is READ: (S_rr, S_rc, S_cc), the window's covariance in pixels^2, r the bitmap's
  *   row and c its column; flux [B,Hh,W] in, out [B,Hh,W] fully written; out must not overlap flux (ART_EINVAL).
  *   B == 0, Hh == 0 or W == 0: ART_OK, nothing launched.  A null pointer, a non-NULL target_dims, B or Hh > 65535 or
@@ -355,6 +356,35 @@ int art_align_bwd(const float *points, const float *normals, const float *orient
  *   supported at every image size and shear (a steeper window only adds tile columns to walk).  A covariance beyond that,
  *   one that is not finite, or one that is not positive semi-definite (S_rr < 0, S_cc < 0 or S_rc^2 > S_rr S_cc (1 + 1e-5))
  *   makes ITS bitmap NaN - marked in the result itself, no host read, no status word; the other bitmaps keep their bits.
+ *
+ * RADIAL WINDOW MODE of art_flux_crop_fwd (the convolved sun for pillbox, Buie and tabulated shapes): crop_width == -2.0 and
+ * crop_height == -(double)K, K an integer, 1 <= K <= 4096.  Each bitmap is convolved with the image of a radial sun shape:
+ *   target_dims is non-NULL and READ as the sun's quantile table t2[0..K] (fp32, rad^2, non-decreasing: t2[k] is the squared
+ *   angular radius below which k/K of the energy lies); centers [B,3] is READ: (M_rr, M_rc, M_cc), the metric M = J J^T of the
+ *   bitmap in pixels^2/rad^2, r the bitmap's row and c its column; flux [B,Hh,W] in, out [B,Hh,W] fully written; out must not
+ *   overlap flux, the table or the metrics (ART_EINVAL).  B == 0, Hh == 0 or W == 0: ART_OK, nothing launched.  A null
+ *   pointer, a crop_height that is not minus an integer, K < 1 or K > 4096, B or Hh > 65535 or Hh * W > 2^30: ART_EINVAL before
+ *   any launch.
+ *   Definition.  Everything that forms the stencil is fp64, from the fp32 inputs read exactly; a weight is rounded to fp32 once;
+ *   the convolution is fp32.
+ *     det = M_rr M_cc - M_rc^2,  q(dr, dc) = (M_cc dr^2 - 2 M_rc dr dc + M_rr dc^2) / det
+ *     node k is the ellipse q <= t2[k], of half extents sqrt(t2[k] M_rr) rows and sqrt(t2[k] M_cc) columns; k* is the largest
+ *       k with t2[k] M_rr <= 64^2 and t2[k] M_cc <= 64^2: at most 129 x 129 taps, the blur mode's own limit
+ *     rho(q) = 1 / (t2[k+1] - t2[k]) for the largest k with t2[k] <= q if 0 <= k < k*, else 0 (so q < t2[0] gives 0)
+ *     raw[dr, dc] = mean over i, j = 0..3 of rho(q(dr + (2i - 3)/8, dc + (2j - 3)/8)), the sixteen values summed as eight pairs
+ *       of opposite points, (i, j) + (3 - i, 3 - j) for i = 0, 1 and j = 0..3 in this order (the tap (-dr, -dc) then sums the
+ *       same pairs in the same order)
+ *     w = raw (k* / K) / sum(raw): the annuli beyond k* are DROPPED - their energy is neither deposited nor renormalised into
+ *       the core; sum(raw) == 0 (a window far below a pixel, a table of zeros): the one tap (0, 0) of weight k* / K
+ *     z[r,c] = sum over dr ascending, then dc ascending, of the taps with w != 0: fma(w[dr, dc], x[r - dr, c - dc], acc)
+ *   (a zero tap between two non-zero ones of a stencil row may be multiplied too: the same bits for a finite x.)  x is zero
+ *   outside the image and z is cut to it.  The stencil is point-symmetric, w[-dr, -dc] == w[dr, dc] exactly, so the operator
+ *   is ITS OWN ADJOINT: its backward pass is the same call on the upstream gradient.
+ *   A metric that is not finite, has M_rr <= 0 or M_cc <= 0 or det <= 1e-6 M_rr M_cc, or for which k* == 0 (not even the first
+ *   annulus fits), makes ITS bitmap NaN; a table that is not finite, has t2[0] < 0 or decreases somewhere makes EVERY bitmap
+ *   NaN - marked in the result itself, no host read, no status word; the other bitmaps keep their bits.
+ *   One kernel, table, stencil and input tile in LDS, no float atomics; a bitmap's bits depend on its own metric, the table and
+ *   (Hh, W) alone - neither on B, nor on its place in the batch, nor on the run.
  * ------------------------------------------------------------------------------------------- */
 int art_flux_crop_fwd(const float *flux, const float *target_dims, int64_t B, int64_t Hh, int64_t W,
                       double crop_width, double crop_height, float *out, float *centers, void *stream);
