@@ -27,6 +27,8 @@ backward, behind ARTIST's own call surface:
                                     (no counterpart) the convolved sun: one chief ray per point and a Gaussian window per bitmap
     artist_amd.radial_blur_flux, optics.radial_window_kept_fraction, Sun.window = "shape"
                                     (no counterpart) the convolved sun for pillbox, Buie and tabulated shapes: a radial window
+    artist_amd.differentiable_blur_flux, Sun.window_gradient
+                                    (no counterpart) the convolved sun's window learns: optical errors from flux images
     artist_amd.EpochGraph           (no counterpart) an epoch captured into a HIP graph and replayed: same bits, one host call
 
 All arithmetic runs in hand-written HIP kernels (``artist_amd/csrc``) reached through the C ABI in
@@ -36,7 +38,7 @@ from ._lib import ArtistHipError, build, lib  # noqa: F401
 from .nurbs import NURBSSurfaces, create_nurbs_evaluation_grid, create_planar_nurbs_control_points  # noqa: F401
 from .flux import (CosineFluxLoss, FocalSpotLoss, JensenShannonLoss, KLDivergenceLoss, PixelLoss, ShapePixelLoss,  # noqa: F401
                    TotalVariationLoss, bitmap_coordinates_to_target_coordinates, blur_flux, crop_and_kl_loss, crop_and_pixel_loss,
-                   crop_flux_distributions_around_center, get_center_of_mass, radial_blur_flux, trapezoid_distribution)
+                   crop_flux_distributions_around_center, differentiable_blur_flux, get_center_of_mass, radial_blur_flux, trapezoid_distribution)
 from .kinematics import Actuators, RigidBody  # noqa: F401
 from .ops import align_surfaces, nurbs_surface_points_and_normals, per_target_sum, perform_canting, trace_rays  # noqa: F401
 from . import optics, optim, training  # noqa: F401

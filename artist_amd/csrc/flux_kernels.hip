@@ -913,6 +913,9 @@ static void launch_crop_bwd_tiled(hipStream_t stream, const float* dims, const f
 // flux_blur_kernels.hip: the blur mode of art_flux_crop_fwd.
 namespace art {
 int flux_blur_launch(const float* x, const float* covariance, int64_t B, int64_t Hh, int64_t W, float* out, hipStream_t stream);
+// ... and the blur mode of art_flux_crop_bwd: the gradient with respect to the covariances.
+int flux_blur_grad_launch(const float* x, const float* covariance, const float* g, int64_t B, int64_t Hh, int64_t W, float* out,
+                          hipStream_t stream);
 // radial_blur_kernels.hip: its radial window mode.
 int flux_radial_blur_launch(const float* x, const float* metric, const float* table, int64_t K, int64_t B, int64_t Hh, int64_t W,
                             float* out, hipStream_t stream);
@@ -957,6 +960,9 @@ extern "C" int art_flux_crop_bwd(const float* flux, const float* target_dims, co
                                  float* grad_flux, float* workspace, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // blur mode: centers holds the windows' covariances and is READ, workspace [B,3] takes the gradient with respect to them
+    if (crop_width == -1.0 && crop_height == -1.0 && !target_dims)
+        return flux_blur_grad_launch(flux, centers, grad_out, B, Hh, W, workspace, stream);
     if (empty_batch(B, Hh, W)) return ART_OK;
     if (!crop_args_ok(flux, target_dims, centers, grad_out, B, Hh, W) || !grad_flux || !workspace) return ART_EINVAL;
     hipLaunchKernelGGL(flux_crop_bwd_com_kernel, dim3((unsigned)B), dim3(kReduceBlock), 0, stream, flux, target_dims, centers,

@@ -139,6 +139,57 @@ def blur_flux(flux: torch.Tensor, covariance: torch.Tensor) -> torch.Tensor:
     return FluxBlur.apply(flux.contiguous(), covariance.contiguous())
 
 
+class DifferentiableFluxBlur(torch.autograd.Function):
+    """``FluxBlur`` with the window learned too: the gradient with respect to the covariances is ``art_flux_crop_bwd`` in its
+    blur mode (crop size (-1, -1), no target dimensions, the covariances where the crop reads its centres, the gradient
+    ``[B,3]`` where it keeps its workspace) - one launch on the sharp bitmaps and the upstream gradient."""
+
+    @staticmethod
+    def covariance_gradient(x: torch.Tensor, covariance: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+        B, Hh, W = x.shape
+        grad = torch.empty((B, 3), dtype=torch.float32, device=x.device)
+        _lib.call("art_flux_crop_bwd", x.device, x.data_ptr(), None, covariance.data_ptr(), B, Hh, W, -1.0, -1.0,
+                  grad_out.data_ptr(), None, grad.data_ptr())
+        return grad
+
+    @staticmethod
+    def forward(ctx, flux, covariance):
+        ctx.learns_window = covariance.requires_grad
+        ctx.save_for_backward(covariance, *((flux,) if ctx.learns_window else ()))
+        return FluxBlur._launch(flux, covariance)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        covariance = ctx.saved_tensors[0]
+        grad_out = grad_out.contiguous()
+        grad_flux = FluxBlur._launch(grad_out, covariance) if ctx.needs_input_grad[0] else None
+        grad_covariance = None
+        if ctx.learns_window and ctx.needs_input_grad[1]:
+            grad_covariance = DifferentiableFluxBlur.covariance_gradient(ctx.saved_tensors[1], covariance, grad_out)
+        return grad_flux, grad_covariance
+
+
+def differentiable_blur_flux(flux: torch.Tensor, covariance: torch.Tensor) -> torch.Tensor:
+    """``blur_flux`` - the same checks, values and bits - differentiable in BOTH arguments: the window learns.
+    The gradient with respect to ``flux`` is the same blur of the upstream gradient, as ``blur_flux`` has it; the gradient with
+    respect to ``covariance [B,3]`` = ``(S_rr, S_rc, S_cc)`` is one launch of ``art_flux_crop_bwd`` in its blur mode (defined in
+    include/artist_hip.h and again, in fp64, in tests/flux_blur_grad_ref.py): the derivative at FIXED tap radii - the radii are
+    piecewise constant in the covariance -, deterministic, without atomics.  A covariance whose bitmap is NaN has a NaN
+    gradient.  When the covariance requires grad the backward pass keeps the sharp ``flux``: 4 ``Hh W`` bytes per bitmap that
+    ``blur_flux`` does not hold; otherwise nothing more is saved and the launches are ``blur_flux``'s.  fp32 on the GPU only
+    (``ArtistHipError`` on the CPU: no CPU fallback); capturable."""
+    if flux.device.type != "cuda" or covariance.device.type != "cuda":
+        raise _lib.ArtistHipError(f"differentiable_blur_flux runs on the GPU only (got tensors on {flux.device} and "
+                                  f"{covariance.device}); there is no CPU fallback")
+    _require_cuda(flux, covariance)
+    if flux.dtype != torch.float32 or covariance.dtype != torch.float32:
+        raise ValueError(f"differentiable_blur_flux takes float32 tensors, got {flux.dtype} and {covariance.dtype}")
+    if flux.dim() != 3 or tuple(covariance.shape) != (flux.shape[0], 3):
+        raise ValueError(f"flux must be [B,Hh,W] and the covariance [B,3], got {tuple(flux.shape)} and {tuple(covariance.shape)}")
+    return DifferentiableFluxBlur.apply(flux.contiguous(), covariance.contiguous())
+
+
 class RadialFluxBlur(torch.autograd.Function):
     """``art_flux_crop_fwd`` in its radial window mode (crop size (-2, -K), the quantile table where the crop reads the target
     dimensions, the metrics where it writes its centres).  The operator is its own adjoint: the backward pass is the same call

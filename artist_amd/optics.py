@@ -22,6 +22,8 @@ angular covariance ``(1, 0, 1)`` it is the metric ``M = J J^T`` of a radial sun'
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 __all__ = ["slant_ranges", "atmospheric_transmittance", "heliostat_intensity_factors", "tilt_normals", "slope_sample",
@@ -138,7 +140,7 @@ def heliostat_intensity_factors(heliostat_group, solar_tower, target_area_indice
 
 def sun_image_covariance(points: torch.Tensor, normals: torch.Tensor, incident: torch.Tensor, target_area_indices: torch.Tensor,
                          centers: torch.Tensor, plane_normals: torch.Tensor, dimensions: torch.Tensor,
-                         angular_covariance: torch.Tensor, resolution) -> torch.Tensor:
+                         angular_covariance: torch.Tensor, resolution, differentiable: bool = False) -> torch.Tensor:
     """``[H,3]`` = ``(S_rr, S_rc, S_cc)`` in pixels^2 (r the bitmap's row, c its column): the covariance of the spot that a
     Gaussian sun of ``angular_covariance`` - ``(C_uu, C_ue, C_ee)`` in rad^2, ``[3]`` or one row per heliostat ``[H,3]``, in the
     ``(u, e)`` order of the distortions - leaves on the planar target of each heliostat, to first order in the tilt of the
@@ -154,7 +156,11 @@ def sun_image_covariance(points: torch.Tensor, normals: torch.Tensor, incident: 
 
     One ``J`` per heliostat: slant range and incidence vary by about a percent across a mirror.  Torch ops in fp64 on a few
     values per heliostat, under ``no_grad``, on the arguments' device, no synchronisation; the result is fp32 and a constant
-    (to first order the image does not depend on the learned surface)."""
+    (to first order the image does not depend on the learned surface).
+
+    ``differentiable=True``: ``J`` is a constant as before, and ``S = J C J^T`` is formed by the same fp64 ops
+    inside the autograd graph of ``angular_covariance`` - the same values, bit for bit, and a gradient for a covariance that
+    learns (a heliostat's optical error through ``C + sigma_h^2 I``)."""
     with torch.no_grad():
         f64 = torch.float64
         # (the sums run in fp64 inside the reduction: no fp64 copy of the surfaces)
@@ -177,6 +183,7 @@ def sun_image_covariance(points: torch.Tensor, normals: torch.Tensor, incident: 
         per_metre = torch.stack(((float(resolution[1]) - 1.0) / size[:, 1], (float(resolution[0]) - 1.0) / size[:, 0]), dim=-1)
         # J [H, (row, column), (u, e)]: row = top - U, column = right - E
         J = -torch.stack((shift[..., 2], shift[..., 0]), dim=1) * per_metre.unsqueeze(-1)
+    with contextlib.nullcontext() if differentiable else torch.no_grad():
         C = angular_covariance.to(device=d.device, dtype=f64)
         if C.shape not in ((3,), (d.shape[0], 3)):
             raise ValueError(f"angular_covariance must be [3] or [{d.shape[0]},3] = (C_uu, C_ue, C_ee), got {tuple(C.shape)}")

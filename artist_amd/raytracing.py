@@ -23,7 +23,7 @@ import torch
 from . import _lib, ops, optics
 from ._memo import Memo
 from .blocking import create_blocking_primitives_rectangles_by_index, create_shading_primitives
-from .flux import blur_flux, radial_blur_flux
+from .flux import blur_flux, differentiable_blur_flux, radial_blur_flux
 from .sampling import DistortionsDataset, RestrictedDistributedSampler
 
 log = logging.getLogger(__name__)
@@ -113,7 +113,18 @@ class HeliostatRayTracer:
     4.17): the window is then the sun's quantile table on the ellipses of the metric ``M = J J^T``
     (``sun_image_covariance`` of the unit covariance, ``flux.radial_blur_flux``), and a heliostat's optical error is a Gaussian
     blur of covariance ``sigma_h^2 M`` on top of it.  Annuli whose ellipse is wider than 64 pixels are dropped, not deposited
-    (``optics.radial_window_kept_fraction``); the other conditions and limits are those above."""
+    (``optics.radial_window_kept_fraction``); the other conditions and limits are those above.
+
+    Optical errors that learn (the sun's ``window_gradient = True``, read with ``integration``): the tracer of a
+    convolved sun then accepts ``active_optical_errors`` that require grad.  ``C_h = C + sigma_h^2 I`` and ``S_h = J_h C_h J_h^T``
+    are formed in the autograd graph (``sun_image_covariance(..., differentiable=True)``) and the blur is
+    ``flux.differentiable_blur_flux``, whose backward pass returns the gradient with respect to the window - so a loss on the
+    flux images reaches ``sigma_h`` without sampling noise (under ``window = "shape"`` through the Gaussian blur of
+    ``sigma_h^2 M`` on top of the radial window, which itself does not learn).  The flux is the flux of the same constants, bit
+    for bit; with constant optical errors, or with none, the launches are those of ``window_gradient = False``.  ``sigma_h = 0``
+    has zero gradient (``dS/dsigma = 2 sigma M``): start from a positive sigma.  The gradient reaches ``group.optical_errors``
+    through ``activate_heliostats``; for a fixed-order sum over a heliostat's activations rebind
+    ``group.active_optical_errors = optics.expand_over_samples(group.optical_errors, counts)``."""
 
     #: publish ``heliostat_group.preferred_reflection_directions`` like the reference does (:285-290)
     publish_reflection_directions = True
@@ -141,6 +152,7 @@ class HeliostatRayTracer:
         # rank, sampling.py:49-53): 8 B per ray of this rank instead of 8 B per ray of the field.
         self.integration = getattr(self.light_source, "integration", "sampled")
         self._radial_window = False     # (set by the checks of a convolved sun)
+        self._window_gradient = False   # (the sun's window_gradient, read with its integration)
         self.distortions_dataset = self._chief_rays(number_of_samples) if self.integration == "convolved" else DistortionsDataset(
             light_source=self.light_source,
             number_of_points_per_heliostat=self.heliostat_group.active_surface_points.shape[1],
@@ -206,6 +218,7 @@ class HeliostatRayTracer:
         dist = getattr(sun, "distribution", None)
         # the window of a radial sun: its own image (Sun.window = "shape"); a normal sun's is the Gaussian either way
         self._radial_window = isinstance(dist, RadialSunShape) and getattr(sun, "window", "gaussian") == "shape"
+        self._window_gradient = bool(getattr(sun, "window_gradient", False))
         if not self._radial_window and not isinstance(dist, torch.distributions.MultivariateNormal):
             raise ValueError("integration='convolved' needs a Gaussian sun (distribution_type 'normal'): the image of a radial sun "
                              "shape (pillbox, Buie, tabulated) is not a Gaussian window; set the sun's window = 'shape' to convolve "
@@ -218,7 +231,7 @@ class HeliostatRayTracer:
             if not isinstance(errors, torch.Tensor) or tuple(errors.shape) != (number_of_samples,):
                 raise ValueError(f"optical_errors must be a tensor with one sigma per active heliostat, shape [{number_of_samples}]; "
                                  f"got {tuple(getattr(errors, 'shape', ()))}")
-            if errors.requires_grad:
+            if errors.requires_grad and not self._window_gradient:
                 raise ValueError("integration='convolved' takes the optical errors as constants (the window is not differentiated): "
                                  "optical_errors.requires_grad must be False")
         if dist.loc.device.type != "cuda":
@@ -236,27 +249,29 @@ class HeliostatRayTracer:
 
     def _angular_covariance(self, idx) -> torch.Tensor:
         """``(C_uu, C_ue, C_ee)`` of the sun (formed when the tracer was built), ``[3]``, or ``[rows,3]`` with the optical errors
-        of this rank's rows as the group holds them now: device ops."""
-        with torch.no_grad():
-            C = self._sun_covariance
-            variance = self._optical_error_variance(idx)
-            if variance is None:
-                return C
-            return torch.stack((C[0] + variance, C[1].expand_as(variance), C[2] + variance), dim=1)
+        of this rank's rows as the group holds them now: device ops, in the autograd graph of optical errors that learn."""
+        C = self._sun_covariance
+        variance = self._optical_error_variance(idx)
+        if variance is None:
+            return C
+        return torch.stack((C[0] + variance, C[1].expand_as(variance), C[2] + variance), dim=1)
 
     def _optical_error_variance(self, idx):
-        """``sigma_h^2 [rows]`` of this rank's rows as the group holds the optical errors now (None: the group has none): device ops."""
-        with torch.no_grad():
-            errors = getattr(self.heliostat_group, "active_optical_errors", None)
-            if errors is None:
-                return None
-            if errors.requires_grad:        # (every activation rebinds the group's tensor: what was checked at construction is gone)
-                raise ValueError("integration='convolved' takes the optical errors as constants: optical_errors.requires_grad "
-                                 "must be False")
-            errors = errors.detach().float().to(self._sun_covariance.device)
-            if idx is not None:
-                errors = errors.index_select(0, idx)
-            return errors * errors           # (no host constant: this runs inside a captured epoch)
+        """``sigma_h^2 [rows]`` of this rank's rows as the group holds the optical errors now (None: the group has none): device
+        ops; part of the autograd graph when the errors learn (the sun's ``window_gradient``) and gradients are recorded."""
+        errors = getattr(self.heliostat_group, "active_optical_errors", None)
+        if errors is None:
+            return None
+        if errors.requires_grad and not self._window_gradient:
+            # (every activation rebinds the group's tensor: what was checked at construction is gone)
+            raise ValueError("integration='convolved' takes the optical errors as constants: optical_errors.requires_grad "
+                             "must be False")
+        if not (errors.requires_grad and torch.is_grad_enabled()):
+            errors = errors.detach()
+        errors = errors.float().to(self._sun_covariance.device)
+        if idx is not None:
+            errors = errors.index_select(0, idx)
+        return errors * errors           # (no host constant: this runs inside a captured epoch)
 
     def get_sampler_indices(self) -> torch.Tensor:
         """Indices of the heliostat samples assigned to this rank (:205-218)."""
@@ -341,11 +356,15 @@ class HeliostatRayTracer:
             flux = radial_blur_flux(flux, metric, self.light_source.distribution.quantile_table)
             variance = self._optical_error_variance(idx)
             if variance is not None:
-                flux = blur_flux(flux, metric * variance.unsqueeze(1))
+                covariance = metric * variance.unsqueeze(1)
+                flux = (differentiable_blur_flux if covariance.requires_grad else blur_flux)(flux, covariance)
         elif convolved:         # the sun's image on each heliostat's target (a new tensor: ops.bitmap_moments has nothing for it)
-            flux = blur_flux(flux, optics.sun_image_covariance(
+            angular = self._angular_covariance(idx)
+            learns = angular.requires_grad       # optical errors that learn: S in the graph, the blur differentiable in it
+            covariance = optics.sun_image_covariance(
                 points, normals, incident_ray_directions, target_area_indices, *_planar_tables(tower, points.device),
-                self._angular_covariance(idx), (width, height)))
+                angular, (width, height), **(dict(differentiable=True) if learns else {}))
+            flux = (differentiable_blur_flux if learns else blur_flux)(flux, covariance)
         if scaled:
             flux, factors = ops.scale_heliostat_rows(flux, factors, extinction_rows, reflectivity_rows)
         if per_target and (scaled or convolved):

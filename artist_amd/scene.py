@@ -206,7 +206,11 @@ class Sun:
     ``window`` (``WINDOWS``) is the convolved sun's window, read with ``integration`` when a tracer is built:
     ``"gaussian"`` (the default) serves Gaussian suns only; with ``"shape"`` a radial sun is convolved with its own image - the
     quantile table on the ellipses of each heliostat's metric (``flux.radial_blur_flux``), annuli wider than 64 pixels dropped
-    (``optics.radial_window_kept_fraction``) - and a normal sun takes the Gaussian window as before."""
+    (``optics.radial_window_kept_fraction``) - and a normal sun takes the Gaussian window as before.
+
+    ``window_gradient`` (a bool, default False), read with ``integration`` when a tracer is built: a convolved
+    sun's tracer then takes optical errors that require grad - each heliostat's ``sigma_h`` enters its Gaussian window and
+    learns from the flux images (``flux.differentiable_blur_flux``).  With constant optical errors it changes nothing."""
 
     def __init__(self, number_of_rays: int, distribution_parameters: dict | None = None,
                  device: torch.device | None = None, sampler: str = "torch") -> None:
@@ -234,6 +238,7 @@ class Sun:
         self.sampler = sampler
         self._integration = "sampled"
         self._window = "gaussian"
+        self._window_gradient = False
 
     @property
     def integration(self) -> str:
@@ -254,6 +259,16 @@ class Sun:
         if name not in WINDOWS:
             raise ValueError(f"Unknown sun window {name!r}; expected one of {WINDOWS}.")
         self._window = name
+
+    @property
+    def window_gradient(self) -> bool:
+        return self._window_gradient
+
+    @window_gradient.setter
+    def window_gradient(self, value: bool) -> None:
+        if not isinstance(value, bool):
+            raise ValueError(f"window_gradient must be True or False, got {value!r}.")
+        self._window_gradient = value
 
     @property
     def sampler(self) -> str:

@@ -357,6 +357,32 @@ int art_align_bwd(const float *points, const float *normals, const float *orient
  *   one that is not finite, or one that is not positive semi-definite (S_rr < 0, S_cc < 0 or S_rc^2 > S_rr S_cc (1 + 1e-5))
  *   makes ITS bitmap NaN - marked in the result itself, no host read, no status word; the other bitmaps keep their bits.
  *
+ * BLUR MODE of art_flux_crop_bwd (the window learns): crop_width == -1.0 && crop_height == -1.0 && target_dims == NULL (with
+ * target dimensions the call is the crop's backward pass, as before, at every crop size).  The gradient of the blur with
+ * respect to its covariances; the gradient with respect to the bitmaps stays the forward call on the upstream gradient.
+ *   flux [B,Hh,W] is the sharp input x; centers [B,3] is READ: (S_rr, S_rc, S_cc); grad_out [B,Hh,W] is the upstream gradient
+ *   g; grad_flux is not touched and may be NULL; workspace is WRITTEN: [B,3] floats (dL/dS_rr, dL/dS_rc, dL/dS_cc), fully
+ *   written - there is no other scratch.  B == 0, Hh == 0 or W == 0: ART_OK, nothing launched.  A null flux, centers, grad_out
+ *   or workspace, the forward's size limits exceeded, or a workspace that overlaps an input: ART_EINVAL before any launch.
+ *   Definition.  Per bitmap L = sum_{r,c} g[r,c] z[r,c], z the blur above, the radii Kr, Ka held FIXED (they are piecewise
+ *   constant in S).  v = S_rr, s = S_rc / S_rr, a = S_cc - S_rc^2 / S_rr.
+ *     derivative taps of a pass of variance u and radius K > 0:  w_k = tap(u)[k], m2 = sum_j w_j j^2,
+ *       w'_k = w_k (k^2 - m2) / (2 u^2)  (they sum to 0); an identity pass (u < 1e-4, K = 0) has w' = 0
+ *     y = the column pass of x with tap(a), y' = the same with w'(a), both on the extended domain
+ *     row tap k sits at pos = -s k, o = floor(pos), f = pos - o
+ *     D_v = sum g[r,c] sum_k w'(v)_k lerp(y [r - k, .], c + pos)
+ *     D_a = sum g[r,c] sum_k w (v)_k lerp(y'[r - k, .], c + pos)
+ *     D_s = sum g[r,c] sum_k w (v)_k (-k) d_k[r - k, c],  d_k the derivative of the lerp with respect to its position:
+ *       y[., c + o + 1] - y[., c + o] where f != 0, and (y[., c + o + 1] - y[., c + o - 1]) / 2 where f == 0 - the mean of
+ *       the two one-sided derivatives (L has a kink there), which covers every tap at s = 0
+ *     dL/dS_rr = D_v - (s / v) D_s + s^2 D_a,   dL/dS_rc = D_s / v - 2 s D_a,   dL/dS_cc = D_a
+ *     S_rr < 1e-4 (the row pass is the identity, a = S_cc): (0, 0, D_a)
+ *   A covariance whose bitmap the forward marks NaN gets (NaN, NaN, NaN); the other bitmaps keep their bits.
+ *   Weights, m2, s, a and the chain rule are fp64 from the fp32 inputs; tap products and per-pixel sums are fp32 in ascending
+ *   k, as in the forward; the product with g is fp32 and the sums over pixels are fp64 in a fixed order.  One kernel, one
+ *   workgroup per bitmap, y and y' in LDS, no atomics, no device allocation, no host read: capturable, and a bitmap's three
+ *   values depend on its own x, g, covariance and (Hh, W) alone.
+ *
  * RADIAL WINDOW MODE of art_flux_crop_fwd (the convolved sun for pillbox, Buie and tabulated shapes): crop_width == -2.0 and
  * crop_height == -(double)K, K an integer, 1 <= K <= 4096.  Each bitmap is convolved with the image of a radial sun shape:
  *   target_dims is non-NULL and READ as the sun's quantile table t2[0..K] (fp32, rad^2, non-decreasing: t2[k] is the squared
